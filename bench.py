@@ -26,10 +26,15 @@ hash-shard of the key space in its own HBM arena (format v4, 128-B slots,
 
 The client streams are the same at every N: at N=1 the set / get batches fan out over
 --writer-streams / --reader-streams HIP streams; at N>1 the owner fans its own ops and the
-request blocks it received out over the same streams (spl_kvs_step_xr).  Outside the timed region:
-the routed step at N=1 (routed_kv_ops_per_s), end-to-end embedding, the embedding daemon's
-own code path per rank (daemon_vectors_per_s), the per-call C API, and config #5's query phase (batched top-k over the search arenas, broadcast + all-gather
-merge at N>1, recall against the exact kernel).
+request blocks it received out over the same streams (spl_kvs_step_xr).
+
+A plain run sets up, warms up, times --steps steps, writes --dump-outputs DIR (what the last timed
+step returned, as .npy) and prints the result line.  With --full it also runs, outside the timed
+region: the integrity check of the last timed step's outputs, config #2's async A/B and the
+exchange A/B (fresh child processes), end-to-end embedding, the embedding daemon's own code path
+per rank (daemon_vectors_per_s), the per-call C API, and config #5's query phase (batched top-k
+over the search arenas, broadcast + all-gather merge at N>1, recall against the exact kernel) and
+mixed steps; without it those rows of the result line are null.
 
 Ops counted exactly as the reference does (every set + get attempt that
 completes, splinter_stress.c:212-213); EAGAIN retries are reported separately.
@@ -51,6 +56,16 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=30)
     p.add_argument("--warmup", type=int, default=3)
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run everything else the benchmark measures or checks (the "
+                        "integrity check of the last timed step, the config #2 async A/B, the per-call C API, "
+                        "end-to-end and daemon embedding, the config #5 query phase and mixed steps, the exchange "
+                        "A/B), each under its own option below; without it a run sets up, warms up, times the steps, "
+                        "writes --dump-outputs and prints the result line with those rows null")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last timed step returned to its caller as DIR/<name>.npy "
+                        "(float32): a fixed, seeded sample of the get rows (values zeroed past their length, statuses, "
+                        "lengths), a sample of the set statuses and the embed batch's vectors and statuses")
     p.add_argument("--mode", default="mixed", choices=["kv", "embed", "mixed"])
     p.add_argument("--keys-per-gpu", type=int, default=100_000_000)
     p.add_argument("--slots-factor", type=float, default=2.0)
@@ -238,7 +253,7 @@ def exchange_ab(args, dev: int, log):
     env.pop("CUDA_VISIBLE_DEVICES", None)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    common = ["--mode", "kv", "--steps", "10", "--warmup", "3", "--host-api", "0", "--host-api-threads2", "0",
+    common = ["--full", "--mode", "kv", "--steps", "10", "--warmup", "3", "--host-api", "0", "--host-api-threads2", "0",
               "--embed-e2e", "0", "--daemon-docs", "0", "--search-keys", "0", "--exchange-ab", "0", "--mixed5", "0",
               "--verify", "5000", "--value-len", str(args.value_len), "--mop", str(args.mop)]
     me = os.path.abspath(__file__)
@@ -287,8 +302,8 @@ def kv_async_ab(args, dev: int, log):
     env.pop("CUDA_VISIBLE_DEVICES", None)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--mode", "kv", "--steps", "10", "--warmup", "3",
-           "--keys-per-gpu", str(args.keys_per_gpu), "--batch", str(args.batch), "--value-len", str(args.value_len),
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--gpus", "1", "--mode", "kv", "--steps", "10",
+           "--warmup", "3", "--keys-per-gpu", str(args.keys_per_gpu), "--batch", str(args.batch), "--value-len", str(args.value_len),
            "--writer-streams", str(args.writer_streams), "--reader-streams", str(args.reader_streams),
            "--host-api", "0", "--host-api-threads2", "0", "--embed-e2e", "0", "--daemon-docs", "0",
            "--search-keys", "0", "--exchange-ab", "0", "--kv-async-ab", "0", "--mixed5", "0", "--verify", "5000"]
@@ -360,7 +375,7 @@ def main():
     # config #2's async form, measured FIRST: each child holds its own 100 M-key arena (~77 GB), which
     # next to this process's KV and search arenas would not fit in one GPU's HBM
     kab = None
-    if world == 1 and args.kv_async_ab and args.mode != "embed" and not args.force_routed:
+    if args.full and world == 1 and args.kv_async_ab and args.mode != "embed" and not args.force_routed:
         kab = kv_async_ab(args, local % max(torch.cuda.device_count(), 1),
                           lambda *a: print(*a, file=sys.stderr, flush=True))
     dev = local % max(torch.cuda.device_count(), 1)
@@ -435,7 +450,7 @@ def main():
         SK = format_keys(n_set, "k", 10, 16, ids=sid)
         GK = format_keys(n_get, "k", 10, 16, ids=gid)
         SV, SL = format_values(n_set, 2 + b, args.value_len, vstride, ids=sid)
-        batches.append((SK, SV, SL, GK, gid))
+        batches.append((SK, SV, SL, GK, gid, sid))
     gout = torch.empty((n_get, vstride), dtype=torch.uint8, device="cuda")
 
     # ---- search arena (config #5 corpus): --search-keys embedded keys per GPU -------------
@@ -552,20 +567,21 @@ def main():
     # so encoder TFLOP/s is quoted over encoder time, not over the mixed step
     emb_events = []
     timing_emb = [False]
+    emb_last = [None]  # (vectors, statuses) the latest embed batch returned (--dump-outputs)
 
     def run_embed():
         if timing_emb[0]:
             e0 = torch.cuda.Event(enable_timing=True)
             e1 = torch.cuda.Event(enable_timing=True)
             e0.record()
-            embedder.run()
+            emb_last[0] = embedder.run()
             e1.record()
             emb_events.append((e0, e1))
         else:
-            embedder.run()
+            emb_last[0] = embedder.run()
 
     def step_local(i):
-        SK, SV, SL, GK, _ = batches[i % nbuf]
+        SK, SV, SL, GK, _, _ = batches[i % nbuf]
         cur = torch.cuda.current_stream()
         if args.throttle and throttle_ev[0] is not None:
             throttle_ev[0].synchronize()
@@ -641,7 +657,7 @@ def main():
     requested = {}  # step -> its request event (issued ahead by the previous step of the same phase)
 
     def _request(i):
-        SK, SV, SL, GK, _ = batches[i % nbuf]
+        SK, SV, SL, GK, _, _ = batches[i % nbuf]
         with torch.cuda.stream(s_req):
             xr.request(i, SK if n_set else None, SV if n_set else None, SL if n_set else None, GK if n_get else None)
             requested[i] = s_req.record_event()
@@ -714,6 +730,58 @@ def main():
     elapsed = t.item()
     attempts, ok, again, miss = [int(x) for x in st.tolist()]
 
+    # ---- --dump-outputs: what the LAST timed step handed back to its caller, as float32 .npy files
+    # (one set per rank, _rank<r> in the name at N>1), so two builds can be compared output for
+    # output.  The 2 GB of get rows are sampled: a fixed, seeded choice of rows, taken among the
+    # gets whose key no set of the same step writes -- a get that races a set of its own key may
+    # return either version, every other row is the same from run to run.  Bytes past a value's
+    # length are unspecified (whatever the row held before) and are zeroed.
+    if args.dump_outputs and args.steps > 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        sfx = f"_rank{rank}" if world > 1 else ""
+
+        def save(name, t):
+            np.save(os.path.join(args.dump_outputs, f"{name}{sfx}.npy"), t.to(torch.float32).cpu().numpy())
+
+        def sample(n, m, seed, among=None):
+            pool = among if among is not None and among.numel() else torch.arange(n, device="cuda")
+            gs = torch.Generator()
+            gs.manual_seed(seed)
+            pos = torch.randint(0, pool.numel(), (min(m, pool.numel()),), generator=gs).sort().values
+            return pool[pos.cuda()]
+
+        last_b = batches[(args.warmup + args.steps - 1) % nbuf]
+        if routed and xr is not None:
+            ss, go, gl, gs_ = r_out[(args.warmup + args.steps - 1) % 2]
+        elif kvs is not None:
+            ss, go, gl, gs_ = s_status, gout, g_lens, g_status
+        else:  # python client streams keep no statuses or lengths: the raw rows
+            ss, go, gl, gs_ = None, (gout if n_get else None), None, None
+        if n_get and go is not None:
+            set_ids = last_b[5]
+            if world > 1:  # every rank's sets of the step (gloo moves host tensors)
+                mine = set_ids if args.backend == "nccl" else set_ids.cpu()
+                parts = [torch.empty_like(mine) for _ in range(world)]
+                dist.all_gather(parts, mine)
+                set_ids = torch.cat(parts).cuda()
+            quiet = torch.nonzero(~torch.isin(last_b[4], set_ids)).squeeze(1)
+            rows = sample(n_get, max(1, 16384 // world), 20240 + rank, among=quiet)
+            vals = go[rows].clone()
+            if gl is not None:
+                ln = torch.where(gs_[rows] == 0, gl[rows], torch.zeros_like(gl[rows]))
+                vals[torch.arange(vals.shape[1], device="cuda")[None, :] >= ln[:, None]] = 0
+                save("get_status", gs_[rows])
+                save("get_lens", ln)
+            save("get_values", vals)
+        if n_set and ss is not None:
+            save("set_status", ss[sample(n_set, max(1, (1 << 20) // world), 30240 + rank)])
+        if embedder is not None:
+            vec, est = emb_last[0] if emb_last[0] is not None else (embedder.out, None)
+            save("embed_vectors", vec)
+            if est is not None:
+                save("embed_status", est)
+
     # ---- integrity: the LAST timed step's own get outputs, sampled over the whole batch, must
     # parse and carry their key's id with a consistent fill (the 'ver:|id:|data:' format is
     # version-independent: any version a racing set wrote is valid), and its sets must have landed
@@ -747,7 +815,7 @@ def main():
     integrity_fail = integrity_rows = timed_set_fail = 0
     integrity_source = None
     last = args.warmup + args.steps - 1
-    if args.verify and n_get:
+    if args.full and args.verify and n_get:
         gid_last = batches[last % nbuf][4]
         m = min(args.verify, n_get)
         sel = torch.linspace(0, n_get - 1, m, device="cuda").long()
@@ -797,11 +865,11 @@ def main():
             log(f"[bench] host-API run failed: {e}")
         return None
 
-    host_api = host_api_run(args.host_api) if args.host_api > 0 and rank == 0 else None
-    host_api2 = host_api_run(args.host_api_threads2) if args.host_api_threads2 > 0 and rank == 0 else None
+    host_api = host_api_run(args.host_api) if args.full and args.host_api > 0 and rank == 0 else None
+    host_api2 = host_api_run(args.host_api_threads2) if args.full and args.host_api_threads2 > 0 and rank == 0 else None
 
     e2e = None
-    if embedder is not None and args.embed_e2e > 0:
+    if args.full and embedder is not None and args.embed_e2e > 0:
         from libsplinter_amd.models.bench_embed import EmbedE2E
         pipe = EmbedE2E(embedder.enc, batch=args.embed_batch, seq=args.embed_seq, rank=rank)
         for _ in range(2):  # warm-up: tokenizer threads, and both key sets' varlen shapes (first-shape GEMM setup)
@@ -828,7 +896,7 @@ def main():
     # ---- the embedding daemon itself, owner computes: each rank's daemon embeds the pending
     # documents of its own store (reference splinference.cpp:500-552)
     daemon = None
-    if embedder is not None and args.daemon_docs > 0:
+    if args.full and embedder is not None and args.daemon_docs > 0:
         daemon = daemon_run(embedder.enc, args.daemon_docs, args.embed_seq, rank, world, routed, f"{node_tag}dm")
 
     # ---- config #5 query phase: batched cosine top-10 over every rank's search arena ---------
@@ -837,7 +905,7 @@ def main():
     # lists are all-gathered and merged (C4).  Recall@10 of the batched path against the exact fp32
     # kernel on the first 16 queries.
     search = None
-    if sarena is not None and args.search_queries > 0 and args.search_batches > 0:
+    if args.full and sarena is not None and args.search_queries > 0 and args.search_batches > 0:
         skv = ShardedKV(GpuShard(sarena))
         gq = torch.Generator(device="cuda")
         gq.manual_seed(4242)
@@ -867,7 +935,7 @@ def main():
     # (the pooling kernel's seqlocked slot write) -> a batched top-10 query over the whole arena with
     # queries built from the vectors just written (each must find its own document first) -------
     mixed5 = None
-    if sarena is not None and embedder is not None and args.mixed5 > 0 and args.search_queries > 0:
+    if args.full and sarena is not None and embedder is not None and args.mixed5 > 0 and args.search_queries > 0:
         skv5 = ShardedKV(GpuShard(sarena))
         nq = args.search_queries
         gq5 = torch.Generator(device="cuda")
@@ -904,7 +972,7 @@ def main():
     # processes, never exec -- a 2-rank KV-only run with both ranks on this device (peer windows; gloo
     # for the small collectives) and a 1-rank run at identical totals
     xab = None
-    if world == 1 and args.exchange_ab and args.mode != "embed":
+    if args.full and world == 1 and args.exchange_ab and args.mode != "embed":
         xab = exchange_ab(args, dev, log)
 
     kv_ops = (n_set + n_get) * args.steps * world
