@@ -105,6 +105,7 @@ struct EpiArgs {
   const uint16_t* lng;   // [N] LN gamma / beta of res (RES_LN_STATS)
   const uint16_t* lnb;
   float2* part;          // [M][N/128] (mean, M2) of out's rows per 128 columns (RES_*STATS)
+  int nsplit;            // k_gemm256: tiles at the end of the dispatch order run as two half-tile blocks
 };
 
 constexpr bool is_fold(int m) { return m == NOMIC_EPI_ROPE_FOLD || m == NOMIC_EPI_SWIGLU_FOLD; }
@@ -421,12 +422,18 @@ __global__ __launch_bounds__(kThreads, 2) void k_gemm_nt(const uint16_t* __restr
 //   staged (RAW: the reading phase first waits vmcnt(#glds issued after it),
 //   then the barrier).  Up to 6 half-tiles (12 DMA per lane) stay in flight.
 // Epilogue: two 128-row halves through one fp32 LDS image (128 x 260).
+// Tail split (EpiArgs::nsplit > 0): a grid whose last round would fill at most half the CUs runs
+// that round's tiles as two half-tile workgroups each (one 128-row half, 3 half-tiles of DMA and
+// 2 quadrant phases per K-tile on a 3-stage LDS ring with its own counted waits: see the half-tile
+// branch of the kernel), so the round takes about half a tile time on twice the CUs.
 // ===========================================================================
 constexpr int kThreads2 = 512;
 constexpr int kHalfBytes = 128 * BK * 2;           // 16 KB
 constexpr int kBufBytes = 4 * kHalfBytes;          // 64 KB
 constexpr int kEpi2Stride = 256 + 4;
 constexpr int kLds2Bytes = (128 * kEpi2Stride * 4 > 2 * kBufBytes) ? 128 * kEpi2Stride * 4 : 2 * kBufBytes;
+constexpr int kLds2SplitBytes = 9 * kHalfBytes;    // 144 KB: the half-tile blocks' 3-stage ring
+static_assert(kLds2SplitBytes >= kLds2Bytes && kLds2SplitBytes <= 160 * 1024, "LDS budget");
 
 __device__ __forceinline__ void wait_vm(int n) {
   switch (n) {  // wave-uniform: scalar branch to an immediate count
@@ -482,8 +489,30 @@ __global__ __launch_bounds__(kThreads2, 1) void k_gemm256(const uint16_t* __rest
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 2, wn = wave & 3;
   int mt, nt;
-  remap_tile(blockIdx.x, mtiles * ntiles, ntiles, ep.gn, mt, nt);
+  // Tail split: blocks [0, T - nsplit) are whole tiles; the last nsplit tiles of the dispatch order
+  // are each computed by two half-tile blocks (qh = their 128-row half) with the highest block
+  // indices, so they are dispatched last.  Whole tiles keep remap_tile's XCD banding.  Half block h
+  // runs on XCD h & 7 (T - nsplit is a multiple of the CU count, hence of 8), so in every whole
+  // group of 16 half blocks, block 8 qh + x takes half qh of the group's tile x: both halves of a
+  // tile run on the XCD whose band the tile belongs to.  The < 16 half blocks left over pair up
+  // (2 u, 2 u + 1) on neighbouring XCDs; they only lose the band's L2 reuse.
+  int bid = blockIdx.x, qh = -1;
+  {
+    const int nw = mtiles * ntiles - ep.nsplit;
+    if (bid >= nw) {
+      const int h = bid - nw, full = (ep.nsplit >> 3) << 4;
+      if (h < full) {
+        bid = nw + ((h >> 4) << 3) + (h & 7);
+        qh = (h >> 3) & 1;
+      } else {
+        bid = nw + (full >> 1) + ((h - full) >> 1);
+        qh = (h - full) & 1;
+      }
+    }
+  }
+  remap_tile(bid, mtiles * ntiles, ntiles, ep.gn, mt, nt);
   const long m0 = (long)mt * 256, n0 = (long)nt * 256;
+  if (qh >= 0 && m0 + qh * 128 >= ep.M) return;  // a half wholly in the row tail (block-uniform)
 
   // per-lane DMA source offsets (elements): half h, instruction i -> 8-row block (i*8 + wave)
   const int srow = lane >> 3, schunk = ((lane & 7) ^ srow) * 8;
@@ -527,11 +556,100 @@ __global__ __launch_bounds__(kThreads2, 1) void k_gemm256(const uint16_t* __rest
         for (int j = 0; j < 2; ++j) acc[a][b][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   const int nk = K / BK;
+  bf16x8 af[4][2], b0[2][2], b1[2][2];
+  if (qh >= 0) {
+    // ---- half-tile workgroup: rows qh*128 .. +127 of the tile, all 256 columns ----------------
+    // LDS = ring of 3 stages x [A<qh> | B0 | B1] half-tiles (48 KB each, 144 KB).  K-tile t lives
+    // in slot t % 3 and is staged, in the order A B0 B1 (6 DMA per lane), during K-tile t - 2.
+    // Per K-tile t: vmcnt(6) (all but K-tile t + 1's six DMAs have landed: K-tile t is in), ONE
+    // barrier, then quadrant (qh, 0) from A, B0 and quadrant (qh, 1) from B1 -- the same K order
+    // and MFMA order per output element as the whole tile, so the bits are the same.
+    //   RAW: K-tile t is read >= one whole K-tile (2 quadrant phases) after its last DMA was
+    //        issued, behind the counted wait and the barrier.
+    //   WAR: slot (t + 2) % 3 held K-tile t - 1, whose last reads every wave finished before it
+    //        reached K-tile t's barrier; the DMAs into it are issued after that barrier.
+    // At most 12 DMA per lane stay in flight.  The accumulators are acc[0][*] for either half.
+    constexpr int kStage3 = 3 * kHalfBytes;
+    const uint32_t oA[2] = {qh ? offA[1][0] : offA[0][0], qh ? offA[1][1] : offA[0][1]};
+    auto hstage = [&](int which, int t, int slot) {  // which: 0 A<qh>, 1 B0, 2 B1
+      const uint16_t* base = (which == 0 ? A : W) + (long)t * BK;
+      char* dst = smem + slot * kStage3 + which * kHalfBytes;
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const uint32_t off = which == 0 ? oA[i] : which == 1 ? offB[0][i] : offB[1][i];
+        if constexpr (PP == 2)
+          spl::glds16_asm(base + off, dst + (i * 8 + wave) * 1024);
+        else
+          __builtin_amdgcn_global_load_lds((gbl_void*)(base + off), (lds_void*)(dst + (i * 8 + wave) * 1024), 16, 0,
+                                           0);
+      }
+    };
+    auto rd = [](bf16x8& dst, const char* p) {
+      dst = *(const bf16x8*)p;
+      __builtin_amdgcn_sched_barrier(0);
+    };
+    auto mm = [&](f32x4 (&ac)[4][2], bf16x8 (&bf)[2][2], int kk) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+          ac[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][kk], bf[j][kk], ac[i][j], 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+    };
+    hstage(0, 0, 0); hstage(1, 0, 0); hstage(2, 0, 0);
+    if (nk > 1) { hstage(0, 1, 1); hstage(1, 1, 1); hstage(2, 1, 1); }
+    int slot = 0, sslot = 2;  // t % 3, (t + 2) % 3
+    auto h_kt = [&](int t, auto n1c, auto n2c) {
+      constexpr bool n1 = decltype(n1c)::value, n2 = decltype(n2c)::value;
+      const char* hA = smem + slot * kStage3;
+      const char* pa = hA + (wr * 64) * 128 + frow;
+      const char* pb0 = hA + kHalfBytes + (wn * 32) * 128 + frow;
+      const char* pb1 = hA + 2 * kHalfBytes + (wn * 32) * 128 + frow;
+      wait_vm(n1 ? 6 : 0);
+      raw_barrier();
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) {
+        const int fs = kk ? fsw1 : fsw0;
+        rd(b0[0][kk], pb0 + fs);
+        rd(b0[1][kk], pb0 + 16 * 128 + fs);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) rd(af[i][kk], pa + i * 16 * 128 + fs);
+      }
+      if constexpr (n2) hstage(0, t + 2, sslot);
+      __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_s_setprio(1);
+      mm(acc[0][0], b0, 0);
+      mm(acc[0][0], b0, 1);
+      __builtin_amdgcn_s_setprio(0);
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) {
+        const int fs = kk ? fsw1 : fsw0;
+        rd(b1[0][kk], pb1 + fs);
+        rd(b1[1][kk], pb1 + 16 * 128 + fs);
+      }
+      if constexpr (n2) hstage(1, t + 2, sslot);
+      __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_s_setprio(1);
+      mm(acc[0][1], b1, 0);
+      __builtin_amdgcn_s_setprio(0);
+      if constexpr (n2) hstage(2, t + 2, sslot);
+      __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_s_setprio(1);
+      mm(acc[0][1], b1, 1);
+      __builtin_amdgcn_s_setprio(0);
+      slot = slot == 2 ? 0 : slot + 1;
+      sslot = sslot == 2 ? 0 : sslot + 1;
+    };
+    int t = 0;
+    for (; t + 2 < nk; ++t) h_kt(t, std::true_type{}, std::true_type{});
+    if (t + 1 < nk) h_kt(t++, std::true_type{}, std::false_type{});
+    if (t < nk) h_kt(t, std::false_type{}, std::false_type{});
+  } else {
   // prologue, in the steady-state issue order: A0 B0 B1 A1 (t=0), A0 B0 B1 (t=1)
   stage(0, 0, 0); stage(2, 0, 0); stage(3, 0, 0); stage(1, 0, 0);
   if (nk > 1) { stage(0, 1, 1); stage(2, 1, 1); stage(3, 1, 1); }
 
-  bf16x8 af[4][2], b0[2][2], b1[2][2];
   // one quadrant's 16 MFMAs (kk, i, j), with the phase's stage issued before them (ILV 0) or
   // between the (kk, i) groups u = ILV and ILV + 4 (ILV > 0)
   auto mma_phase = [&](f32x4 (&ac)[4][2], bf16x8 (&bf)[2][2], int which, int st, int sbuf, bool go) {
@@ -768,9 +886,10 @@ __global__ __launch_bounds__(kThreads2, 1) void k_gemm256(const uint16_t* __rest
     // ---- phase 4: quadrant (1,1), registers only (B1's last read was phase 2: a barrier ago)
     mma_phase(acc[1][1], b1, 3, t + 2, buf, n2);
   }
+  }  // whole tile
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
-  if constexpr (MODE == NOMIC_EPI_SWIGLU && EPI == 1) {
+  if constexpr (MODE == NOMIC_EPI_SWIGLU && EPI == 1) {  // (whole tiles only: never launched with a tail split)
     constexpr int kS = 128 + 8;  // bf16 row stride of the image (272 B: conflict-free 4-B writes)
     uint16_t* E16 = (uint16_t*)smem;
     const int fq = lane >> 4, fr = lane & 15;
@@ -808,10 +927,13 @@ __global__ __launch_bounds__(kThreads2, 1) void k_gemm256(const uint16_t* __rest
   }
 
   // ---- epilogue: two 128-row halves through the fp32 LDS image ------------
+  // (a half-tile block holds its one half in acc[0] and runs the first pass only, on rows of qh)
   float* E = (float*)smem;
   const int fq = lane >> 4, fr = lane & 15;
+  const long mbase = m0 + (qh > 0 ? 128 : 0);
 #pragma unroll
   for (int qm = 0; qm < 2; ++qm) {
+    if (qm == 1 && qh >= 0) break;
     __syncthreads();
 #pragma unroll
     for (int qn = 0; qn < 2; ++qn)
@@ -823,7 +945,7 @@ __global__ __launch_bounds__(kThreads2, 1) void k_gemm256(const uint16_t* __rest
           for (int r = 0; r < 4; ++r)
             E[(wr * 64 + i * 16 + fq * 4 + r) * kEpi2Stride + qn * 128 + wn * 32 + j * 16 + fr] = acc[qm][qn][i][j][r];
     __syncthreads();
-    const long mh = m0 + qm * 128;
+    const long mh = mbase + qm * 128;
     if constexpr (MODE == NOMIC_EPI_STORE || MODE == NOMIC_EPI_RESIDUAL) {
 #pragma unroll
       for (int it = 0; it < (128 * 256 / 8) / kThreads2; ++it) {
@@ -911,7 +1033,33 @@ __global__ __launch_bounds__(kThreads2, 1) void k_gemm256(const uint16_t* __rest
 
 namespace {
 
-int g_num_cus = 256;  // MI355X: 256 CUs in 8 XCDs; refreshed from the device on first use
+int g_num_cus = 0;  // MI355X: 256 CUs in 8 XCDs; read from the device on first use
+int num_cus() {
+  if (g_num_cus <= 0) {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
+      n = 256;
+    g_num_cus = n;
+  }
+  return g_num_cus;
+}
+
+// Tail split of the 256^2 kernel (NOMIC_GEMM_TAIL_SPLIT, nomic_gemm_set_tail_split): 1 = a last
+// round of R <= CUs / 2 tiles runs as 2 R half-tile blocks of the same launch; 0 = one block per tile
+int g_tail_split = -1;
+int tail_split() {
+  if (g_tail_split < 0) {
+    const char* e = getenv("NOMIC_GEMM_TAIL_SPLIT");
+    g_tail_split = e && *e ? atoi(e) != 0 : 1;
+  }
+  return g_tail_split;
+}
+// tiles of a T-tile grid that run as two half-tile blocks
+int split_tiles(long T) {
+  const int cus = num_cus(), R = (int)(T % cus);
+  return tail_split() && R > 0 && R <= cus / 2 ? R : 0;
+}
 
 template <typename F>
 void allow_lds(F* f, int bytes) {
@@ -966,15 +1114,17 @@ int launch(const uint16_t* A, long lda, const uint16_t* W, long ldw, long M, int
   }();
   if (k256_ok && fits && (var == 256 || (var == 0 && tiles256 >= min_tiles))) {
     static bool attr = [] {
-      allow_lds(k_gemm256<MODE, 0, 0, 2>, kLds2Bytes);
+      allow_lds(k_gemm256<MODE, 0, 0, 2>, kLds2SplitBytes);
       return true;
     }();
     (void)attr;
     const int mtiles = (int)(mpad / 256), ntiles = N / 256;
     ep.gn = band_width(ntiles, 4);
+    ep.nsplit = split_tiles(tiles256);
+    // a launch without half-tile blocks is what it was: same grid, same LDS size
     if constexpr (k256_ok)
-      hipLaunchKernelGGL((k_gemm256<MODE, 0, 0, 2>), dim3(mtiles * ntiles), dim3(kThreads2), kLds2Bytes, s, A, lda, W,
-                         ldw, K, mtiles, ntiles, ep);
+      hipLaunchKernelGGL((k_gemm256<MODE, 0, 0, 2>), dim3(mtiles * ntiles + ep.nsplit), dim3(kThreads2),
+                         ep.nsplit ? kLds2SplitBytes : kLds2Bytes, s, A, lda, W, ldw, K, mtiles, ntiles, ep);
     return (int)hipGetLastError();
   }
   const int mtiles = (int)((M + BM - 1) / BM), ntiles = N / BN;
@@ -991,6 +1141,18 @@ extern "C" int nomic_gemm_set_variant(int variant) {
   const int prev = gemm_variant();
   g_variant = variant == 128 || variant == 256 ? variant : 0;
   return prev;
+}
+
+extern "C" int nomic_gemm_set_tail_split(int on) {
+  const int prev = tail_split();
+  g_tail_split = on != 0;
+  return prev;
+}
+
+extern "C" long nomic_gemm256_grid(long M, int N) {
+  if (M <= 0 || N <= 0 || N % 256) return 0;
+  const long T = (M + 255) / 256 * (N / 256);
+  return T + split_tiles(T);
 }
 
 extern "C" int nomic_gemm_ln(int mode, const void* A, long lda, const void* W, long ldw, long M, int N, int K,

@@ -13,7 +13,8 @@
 // v_mfma_f32_16x16x32_bf16 (192 fp32 accumulators per lane).  At M = 32768 tokens the grid is
 // exactly 256 workgroups: one per CU, no tail wave.  The MFMA operands are swapped (the W fragment
 // is the A operand), so a lane's accumulator holds four CONSECUTIVE output columns of one row:
-// residual loads, LayerNorm and the bf16 stores work on 8-byte row pieces straight from registers.
+// residual loads, LayerNorm and the bf16 stores work on 8-byte row pieces straight from registers
+// (16-byte pieces in the default form, after lanes l and l ^ 16 exchange halves: EPI 4 below).
 //
 // K loop: BK = 32 (one MFMA k-step), two LDS buffers of [A 128 x 32 | W 768 x 32] bf16 (56 KB
 // each), filled by global_load_lds_dwordx4 (LDS-DMA; 7 wave-instructions per wave per stage) one
@@ -51,13 +52,7 @@ constexpr int kRowBytes = kBK * 2;                   // 64
 constexpr int kABytes = kBM * kRowBytes;             // 8 KB per A stage
 constexpr int kWBytes = kN * kRowBytes;              // 48 KB per W stage
 constexpr int kGldsW = kWBytes / 1024 / 8;           // W wave-instructions per wave per stage (6)
-// epilogue staging: half a tile (64 rows x 768 bf16, rows padded to 1552 B) + two [4][64] fp32
-// reduction arrays
-constexpr int kHalfRows = 64;
-constexpr int kOutRowBytes = kN * 2;                  // 1536
-constexpr int kRowPitch = kOutRowBytes + 16;          // 1552: 16 rows of one column -> 16 bank groups
-constexpr int kHalfBytes = kHalfRows * kRowPitch;     // 97 KB
-constexpr int kEpiLds = kHalfBytes + 2 * 4 * kHalfRows * 4;
+constexpr int kEpiLds = 4 * kBM * 4;                 // epilogue: [4 column waves][128 rows] fp32 row sums
 
 // K pipelines (template PIPE): LDS rings of NW W-stages and NA A-stages, one barrier per stage.
 // Iteration t, after its barrier, issues the stages W(t + NW - 1) and A(t + NA - 1) (the one with
@@ -100,6 +95,10 @@ __device__ __forceinline__ void wait_vm(int n) {
   }
 }
 
+// the value of lane ^ 16 (ds_swizzle bit mode: and 0x1f, or 0, xor 0x10 -- a cross-lane move
+// on the LDS crossbar that touches no LDS memory)
+__device__ __forceinline__ uint32_t xor16(uint32_t v) { return (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x401F); }
+
 // physical 16-B chunk of logical chunk c in 64-B row r
 __device__ __forceinline__ int swz(int r, int c) { return c ^ ((r >> 1) & 3); }
 
@@ -111,15 +110,21 @@ __device__ __forceinline__ int swz(int r, int c) { return c ^ ((r >> 1) & 3); }
 // instructions ahead of each group of 8 MFMAs, in issue order) instead of all issued after the
 // barrier, where they held both waves of a SIMD off the matrix core for the ~100-cycle issue cost
 // of each DMA instruction.  ILV 0: all after the barrier.
-// EPI 0: residual added in the epilogue (8-B loads); 1: LDS-staged epilogue; 2: the residual is
+// EPI 0: residual added in the epilogue (8-B loads); 2: the residual is
 // the first K step -- one MFMA per tile against an identity operand (acc = I . R, exact: 1.0 x a
 // bf16 value) with R fragments loaded in the prologue beside the first stages, so the epilogue
 // reads nothing.  3 (K = 768, the o-proj): the residual is added during the K loop -- stage t
 // loads the lane's residual pieces of two of its 48 (m-tile, n-tile) accumulator tiles, stage t + 1
 // adds them -- so the epilogue only normalises and stores: the residual's 50 MB at M = 32768 no
 // longer arrive while every workgroup sits in its epilogue (o-proj 62.6 -> 56.3 us; the down
-// projection, K = 3072, gains nothing from it: 146.3 vs 147.1 us, profiles/r4aq).  PF: W fragment pairs read PF pairs
-// ahead of their MFMAs.
+// projection, K = 3072, gains nothing from it: 146.3 vs 147.1 us, profiles/r4aq).  4: EPI 0 with
+// 16-B residual loads and output stores from registers (24 of each per lane instead of 48 8-B
+// ones; lane pairs l, l ^ 16 exchange halves, see the epilogue): o-proj 64.0 -> 51.4 us, down
+// 149.8 -> 138.0 us, the same bits (profiles/encoder_tails).  It needs 16-B aligned residual and
+// output rows; the entry point runs EPI 0 where they are not.  (16-B stores on EPI 3 measured 57.9
+// us on the o-proj, no better than EPI 3 itself; an LDS-staged 16-B epilogue spilled 109 registers
+// into the K loop and took 420 us on the down shape: both are gone.)
+// PF: W fragment pairs read PF pairs ahead of their MFMAs.
 // AS: the K-loop's LDS-DMAs issued from inline asm (glds_asm.hpp: counted lgkmcnt before the MFMAs)
 // ROT: block b walks the K steps starting at step b mod nk (the sum is order-free up to fp32 rounding), so
 // the 256 blocks that start together fetch different W stages instead of all hitting the same L2 lines
@@ -136,8 +141,10 @@ __global__ __launch_bounds__(256 * WM, 1) void k_gemm_rln(const uint16_t* __rest
   constexpr int kWaves = 4 * WM, kNThreads = 64 * kWaves;
   constexpr int RW = kBM / WM, MT = RW / 16;           // rows and m-tiles per wave
   constexpr int GA = 8 / kWaves, GW = 48 / kWaves;     // LDS-DMA wave-instructions per wave per stage
-  static_assert(EPI == 0 || WM == 2, "the LDS-staged epilogue splits the tile by wave rows");
-  static_assert(EPI != 3 || MT * kNT == 48, "EPI 3 spreads 48 accumulator tiles over 24 stages");
+  constexpr bool KRES = EPI == 3;  // residual added during the K loop
+  constexpr bool WIDE = EPI == 4;  // 16-B epilogue I/O from registers
+  static_assert(EPI == 0 || EPI == 2 || EPI == 3 || EPI == 4, "epilogue forms");
+  static_assert(!KRES || MT * kNT == 48, "EPI 3 spreads 48 accumulator tiles over 24 stages");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = WM == 2 ? wave >> 2 : 0, wn = wave & 3;
@@ -265,7 +272,7 @@ __global__ __launch_bounds__(256 * WM, 1) void k_gemm_rln(const uint16_t* __rest
   for (int t = 0; t < nk; ++t) {
     wait_vm(younger(t));
     raw_barrier();  // stage t visible to every wave; every wave is done with stage t-1's slots
-    if (EPI == 3 && t < 24) {
+    if (KRES && t < 24) {
       // loaded one stage ahead of their add, issued before this stage's DMAs (older than them: the
       // counted waits above stay exact); a chain of uniform branches keeps the tile indices static
 #pragma unroll
@@ -328,7 +335,7 @@ __global__ __launch_bounds__(256 * WM, 1) void k_gemm_rln(const uint16_t* __rest
       for (int u = (kNT / 2) * ILV; u < kOps; ++u) issue_op(t, u);
     }
   }
-  if constexpr (EPI == 3) {  // the last pair (loaded at stage 23)
+  if constexpr (KRES) {  // the last pair (loaded at stage 23)
     res_add(46, rq[0]);
     res_add(47, rq[1]);
   }
@@ -338,11 +345,43 @@ __global__ __launch_bounds__(256 * WM, 1) void k_gemm_rln(const uint16_t* __rest
   // ---- epilogue -------------------------------------------------------------------------
   // lane: rows m_i = m0 + wr*64 + i*16 + (lane & 15); columns n_j = wn*192 + j*16 + (lane>>4)*4 + 0..3
   const int rl = lane & 15, cq = (lane >> 4) * 4;
-  if constexpr (EPI != 1) {
-    // direct: residual loads (EPI 0; EPI 2 has it in the accumulators) and 8-B stores from registers
+  {
+    // residual loads (EPI 0 / 4; EPI 2 and 3 have it in the accumulators) and stores from
+    // registers, in 8-B (EPI 0, 2, 3) or 16-B (EPI 4) row pieces
     float* red = (float*)smem;  // [4 column waves][128 rows]
     const long mb = m0 + wr * RW + rl;  // row of m-tile i: mb + 16 i
     float s[MT] = {};
+    // WIDE: lanes l and l ^ 16 hold adjacent 4-column groups of one row.  For the n-tile pair
+    // (2p, 2p + 1) the even 16-lane group takes the pair's 8 consecutive columns of tile 2p and the
+    // odd group those of tile 2p + 1: one 16-B access per lane and pair, and the half that belongs
+    // to the partner lane changes hands by ds_swizzle (lane ^ 16, no LDS memory).  Every value is
+    // added and summed in the order of the 8-B form (per row: n-tiles ascending), so the bits match.
+    const bool odd = (lane >> 4) & 1;
+    const int c8 = wn * kWN + (odd ? 16 : 0) + (lane >> 5) * 8;  // + 32 p: the lane's 8 columns of pair p
+    (void)odd, (void)c8;
+    if constexpr (EPI == 4) {
+#pragma unroll
+      for (int p = 0; p < kNT / 2; ++p) {
+#pragma unroll
+        for (int i = 0; i < MT; ++i) {
+          const long m = mb + 16 * i < M ? mb + 16 * i : M - 1;
+          const uint4 rr = *(const uint4*)(res + m * ldr + c8 + 32 * p);
+          const uint32_t gx = xor16(odd ? rr.x : rr.z), gy = xor16(odd ? rr.y : rr.w);
+          const uint32_t r0[2] = {odd ? gx : rr.x, odd ? gy : rr.y};  // tile 2p
+          const uint32_t r1[2] = {odd ? rr.z : gx, odd ? rr.w : gy};  // tile 2p + 1
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            const int j = 2 * p + h;
+            const uint32_t x = h ? r1[0] : r0[0], y = h ? r1[1] : r0[1];
+            acc[i][j][0] += bf2f(x & 0xffff);
+            acc[i][j][1] += bf2f(x >> 16);
+            acc[i][j][2] += bf2f(y & 0xffff);
+            acc[i][j][3] += bf2f(y >> 16);
+            s[i] += (acc[i][j][0] + acc[i][j][1]) + (acc[i][j][2] + acc[i][j][3]);
+          }
+        }
+      }
+    } else {
 #pragma unroll
     for (int j = 0; j < kNT; ++j) {
       const int n = wn * kWN + j * 16 + cq;
@@ -359,6 +398,7 @@ __global__ __launch_bounds__(256 * WM, 1) void k_gemm_rln(const uint16_t* __rest
         (void)n;
         s[i] += (acc[i][j][0] + acc[i][j][1]) + (acc[i][j][2] + acc[i][j][3]);
       }
+    }
     }
 #pragma unroll
     for (int i = 0; i < MT; ++i) {
@@ -404,6 +444,36 @@ __global__ __launch_bounds__(256 * WM, 1) void k_gemm_rln(const uint16_t* __rest
       const float var = (red[r] + red[kBM + r] + red[2 * kBM + r] + red[3 * kBM + r]) * (1.f / kN);
       rstd[i] = rsqrtf(var + eps);
     }
+    if constexpr (WIDE) {
+#pragma unroll
+      for (int p = 0; p < kNT / 2; ++p) {
+        float g[2][4], be[2][4];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const int n = wn * kWN + (2 * p + h) * 16 + cq;
+          const uint2 gg = *(const uint2*)(gamma + n), bb = *(const uint2*)(beta + n);
+          g[h][0] = bf2f(gg.x & 0xffff), g[h][1] = bf2f(gg.x >> 16), g[h][2] = bf2f(gg.y & 0xffff), g[h][3] = bf2f(gg.y >> 16);
+          be[h][0] = bf2f(bb.x & 0xffff), be[h][1] = bf2f(bb.x >> 16), be[h][2] = bf2f(bb.y & 0xffff), be[h][3] = bf2f(bb.y >> 16);
+        }
+#pragma unroll
+        for (int i = 0; i < MT; ++i) {
+          const long m = mb + 16 * i;
+          uint32_t pk[2][2];
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            float o[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[e] = (acc[i][2 * p + h][e] - mean[i]) * rstd[i] * g[h][e] + be[h][e];
+            pk[h][0] = pk2(o[0], o[1]);
+            pk[h][1] = pk2(o[2], o[3]);
+          }
+          // the even group keeps tile 2p and gets the partner's four columns of it, the odd group 2p + 1
+          const uint32_t gx = xor16(odd ? pk[0][0] : pk[1][0]), gy = xor16(odd ? pk[0][1] : pk[1][1]);
+          const uint4 v = odd ? make_uint4(gx, gy, pk[1][0], pk[1][1]) : make_uint4(pk[0][0], pk[0][1], gx, gy);
+          if (m < M) *(uint4*)(out + m * ldo + c8 + 32 * p) = v;
+        }
+      }
+    } else {
 #pragma unroll
     for (int j = 0; j < kNT; ++j) {
       const int n = wn * kWN + j * 16 + cq;
@@ -419,129 +489,24 @@ __global__ __launch_bounds__(256 * WM, 1) void k_gemm_rln(const uint16_t* __rest
         if (m < M) *(uint2*)(out + m * ldo + n) = make_uint2(pk2(o[0], o[1]), pk2(o[2], o[3]));
       }
     }
-  } else {
-    // LDS-staged, one 64-row half at a time: the residual half-tile comes in by LDS-DMA with every
-    // request in flight at once (whole rows in 16-B pieces), the waves that own the half add it and
-    // normalise in registers, write bf16 back in place, and all 512 threads store whole rows with
-    // 16-B stores.  Rows are padded to 1552 B, so the 16 lanes that read one column of 16 rows hit 16
-    // different bank groups and every (m-tile, n-tile) element of a lane sits at a fixed offset
-    // from one base address.  A padded row cannot take a 1-KB DMA piece across its end: each row is
-    // one 64-lane piece (bytes 0-1023) and one 32-lane piece (1024-1535).
-    char* R = smem;
-    float* red1 = (float*)(smem + kHalfBytes);
-    float* red2 = red1 + 4 * kHalfRows;
-    const int ebase = rl * kRowPitch + (wn * kWN + cq) * 2;  // + i*16 rows + j*16 columns
-#pragma unroll 1
-    for (int h = 0; h < 2; ++h) {
-      const long mh = m0 + h * kHalfRows;
-#pragma unroll 1
-      for (int u = 0; u < kHalfRows / 8; ++u) {
-        const int row = wave * 8 + u;
-        const long gr = mh + row < M ? mh + row : M - 1;
-        const uint16_t* src = res + gr * ldr + lane * 8;
-        __builtin_amdgcn_global_load_lds((gbl_void*)src, (lds_void*)(R + row * kRowPitch), 16, 0, 0);
-        if (lane < 32)
-          __builtin_amdgcn_global_load_lds((gbl_void*)(src + 512), (lds_void*)(R + row * kRowPitch + 1024), 16, 0, 0);
-      }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      const bool mine = wr == h;
-      float mean[4], rstd[4];
-      if (mine) {
-        float sm[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int j = 0; j < kNT; ++j) {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const uint2 rr = *(const uint2*)(R + ebase + i * 16 * kRowPitch + j * 32);
-            acc[i][j][0] += bf2f(rr.x & 0xffff);
-            acc[i][j][1] += bf2f(rr.x >> 16);
-            acc[i][j][2] += bf2f(rr.y & 0xffff);
-            acc[i][j][3] += bf2f(rr.y >> 16);
-            sm[i] += (acc[i][j][0] + acc[i][j][1]) + (acc[i][j][2] + acc[i][j][3]);
-          }
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          sm[i] += __shfl_xor(sm[i], 16);
-          sm[i] += __shfl_xor(sm[i], 32);
-          if (lane < 16) red1[wn * kHalfRows + i * 16 + rl] = sm[i];
-        }
-      }
-      __syncthreads();
-      if (mine) {
-        float sq[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int r = i * 16 + rl;
-          mean[i] = (red1[r] + red1[kHalfRows + r] + red1[2 * kHalfRows + r] + red1[3 * kHalfRows + r]) * (1.f / kN);
-        }
-#pragma unroll
-        for (int j = 0; j < kNT; ++j)
-#pragma unroll
-          for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              const float d = acc[i][j][e] - mean[i];
-              sq[i] += d * d;
-            }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          sq[i] += __shfl_xor(sq[i], 16);
-          sq[i] += __shfl_xor(sq[i], 32);
-          if (lane < 16) red2[wn * kHalfRows + i * 16 + rl] = sq[i];
-        }
-      }
-      __syncthreads();
-      if (mine) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int r = i * 16 + rl;
-          const float var = (red2[r] + red2[kHalfRows + r] + red2[2 * kHalfRows + r] + red2[3 * kHalfRows + r]) *
-                            (1.f / kN);
-          rstd[i] = rsqrtf(var + eps);
-        }
-#pragma unroll
-        for (int j = 0; j < kNT; ++j) {
-          const int n = wn * kWN + j * 16 + cq;
-          const uint2 gg = *(const uint2*)(gamma + n), bb = *(const uint2*)(beta + n);
-          const float g[4] = {bf2f(gg.x & 0xffff), bf2f(gg.x >> 16), bf2f(gg.y & 0xffff), bf2f(gg.y >> 16)};
-          const float be[4] = {bf2f(bb.x & 0xffff), bf2f(bb.x >> 16), bf2f(bb.y & 0xffff), bf2f(bb.y >> 16)};
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            float o[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = (acc[i][j][e] - mean[i]) * rstd[i] * g[e] + be[e];
-            *(uint2*)(R + ebase + i * 16 * kRowPitch + j * 32) = make_uint2(pk2(o[0], o[1]), pk2(o[2], o[3]));
-          }
-        }
-      }
-      __syncthreads();
-      // the normalised half -> global, whole rows in 16-B pieces
-#pragma unroll 2
-      for (int u = 0; u < kHalfRows * 96 / kThreads; ++u) {
-        const int L = u * kThreads + tid;
-        const int row = L / 96, pc = L - row * 96;
-        const uint4 v = *(const uint4*)(R + row * kRowPitch + pc * 16);
-        if (mh + row < M) *(uint4*)(out + (mh + row) * ldo + pc * 8) = v;
-      }
-      __syncthreads();  // R is refilled by the next half
     }
   }
 }
 
-// Two selectable forms (NOMIC_RLN): 222 (default) = PIPE 2 (3 W stages, 2 A stages), DMA
-// interleave 2, residual added in the epilogue; 232 = the same with the residual added during the
+// Selectable forms (NOMIC_RLN), all PIPE 2 (3 W stages, 2 A stages) with DMA interleave 2: 242
+// (default) = residual added in the epilogue, 16-B residual loads and output stores; 222 = the
+// same with 8-B loads and stores (the default until the 16-B form: mixed step 11.89-11.92 ->
+// 11.69-11.74 ms, profiles/encoder_tails); 232 = 222 with the residual added during the
 // K loop at K = 768 (EPI 3): 10 % faster on the o-proj with a cold residual (profiles/r4aq), but in
 // the encoder the residual was just written by the previous layer and is warm, and the mixed step
 // measured 12.452 (222) vs 12.500 ms (232) over three alternating runs each (profiles/r4ax).  The
 // other A/B forms of round 3 are gone; their measurements stay in profiles/r3_rln_*.
 int g_rln_variant = -1;
-int rln_pick(int v) { return v == 232 ? 232 : 222; }
+int rln_pick(int v) { return v == 222 || v == 232 ? v : 242; }
 int rln_variant() {
   if (g_rln_variant < 0) {
     const char* e = getenv("NOMIC_RLN");
-    g_rln_variant = rln_pick(e && *e ? atoi(e) : 222);
+    g_rln_variant = rln_pick(e && *e ? atoi(e) : 242);
   }
   return g_rln_variant;
 }
@@ -580,7 +545,13 @@ extern "C" int nomic_gemm_res_ln(const void* A, long lda, const void* W, long ld
   const auto* g = (const uint16_t*)gamma;
   const auto* b = (const uint16_t*)beta;
   auto* o = (uint16_t*)out;
-  if (rln_variant() == 232 && K / kBK >= 24 && K <= 768) launch_rln<2, 3, 2, 2>(blocks, s, a, lda, w, ldw, K, M, r, ldr, g, b, eps, o, ldo);
+  // 16-B epilogue accesses need 16-B aligned rows; where they are not, the 8-B form runs
+  const bool wide_ok = ldr % 8 == 0 && ldo % 8 == 0 && ((uintptr_t)res | (uintptr_t)out) % 16 == 0;
+  int v = rln_variant();
+  if (v == 232 && !(K / kBK >= 24 && K <= 768)) v = 222;
+  if (v == 242 && !wide_ok) v = 222;
+  if (v == 232) launch_rln<2, 3, 2, 2>(blocks, s, a, lda, w, ldw, K, M, r, ldr, g, b, eps, o, ldo);
+  else if (v == 242) launch_rln<2, 4, 2, 2>(blocks, s, a, lda, w, ldw, K, M, r, ldr, g, b, eps, o, ldo);
   else launch_rln<2, 0, 2, 2>(blocks, s, a, lda, w, ldw, K, M, r, ldr, g, b, eps, o, ldo);
   return (int)hipGetLastError();
 }

@@ -46,6 +46,14 @@ int nomic_row_stats(const float *part, int nparts, long M, float eps, float *st,
  * epilogue, 256 = launch-per-tile 256x256 phased kernel, 128 = 128x128 (where the
  * shape allows; otherwise the next one that does).  Returns the previous setting. */
 int nomic_gemm_set_variant(int variant);
+/* Tail split of the 256x256 kernel (default on; env NOMIC_GEMM_TAIL_SPLIT=0 turns it off): when the
+ * last round of the grid would fill at most half the CUs (0 < tiles % CUs <= CUs / 2), its tiles
+ * run as two 128-row half-tile workgroups each, in the same launch; the output bits do not change.
+ * Returns the previous setting. */
+int nomic_gemm_set_tail_split(int on);
+/* workgroups the 256x256 kernel launches for an [M, N] output under the current setting: tiles,
+ * plus one per split tile (0: N is no multiple of 256) */
+long nomic_gemm256_grid(long M, int N);
 
 /* x[t] = LN(tok[ids[t]] + type_row) ; bf16 out [T, 768] */
 int nomic_embed_ln(const int32_t *ids, long T, const void *tok_emb, const void *type_row,

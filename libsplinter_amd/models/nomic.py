@@ -82,6 +82,10 @@ def _lib():
         L.nomic_row_stats.restype = c_int
         L.nomic_gemm_set_variant.argtypes = [c_int]
         L.nomic_gemm_set_variant.restype = c_int
+        L.nomic_gemm_set_tail_split.argtypes = [c_int]
+        L.nomic_gemm_set_tail_split.restype = c_int
+        L.nomic_gemm256_grid.argtypes = [c_long, c_int]
+        L.nomic_gemm256_grid.restype = c_long
         L.nomic_attention_set_variant.argtypes = [c_int]
         L.nomic_attention_set_variant.restype = c_int
         L.nomic_embed_ln.argtypes = [P, c_long, P, P, P, P, c_float, P, P]

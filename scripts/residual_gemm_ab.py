@@ -22,8 +22,9 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--no-blas", action="store_true")
-    ap.add_argument("--rln-variants", default="11", help="comma list of nomic_gemm_res_ln variants "
-                    "(PIPE*10 + EPI, csrc/hip/gemm_rln.hip) timed as separate arms")
+    ap.add_argument("--rln-variants", default="222,242", help="comma list of nomic_gemm_res_ln forms (NOMIC_RLN, "
+                    "csrc/hip/gemm_rln.hip rln_pick: 242 the 16-B epilogue default, 222, 232) timed as "
+                    "separate arms")
     ap.add_argument("--ks", default="", help="comma list of K values to time instead of the o-proj / down shapes "
                     "(per-tile fixed cost = intercept of time vs K)")
     a = ap.parse_args()
