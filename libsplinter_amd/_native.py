@@ -256,6 +256,7 @@ def _declare_hip(L):
         _sig(L, "spl_hbm_ring_hold", c_int, c_void_p, c_int)
     _sig(L, "spl_arena_purge", c_int, A, P)
     _sig(L, "spl_arena_vec16_rebuild", c_int, A, P)
+    _sig(L, "spl_arena_vec8_rebuild", c_int, A, P)
     _sig(L, "spl_arena_probe_stats", c_int, A, P, P)
     _sig(L, "spl_hbm_probe_stats", c_int, P, P)
     _sig(L, "spl_hbm_rehash", c_int, P, P)

@@ -1222,6 +1222,14 @@ int cmd_stats(int, char**) {
   }
   // probe-chain health of an hbm: / node: store (libsplinter_hip.so, one device pass): how far a hit
   // and a miss probe, and the tombstones that make misses walk further
+  // which copies of the vectors the arena carries (a node: the ones every shard carries): the batched
+  // search streams the smallest
+  using CopiesFn = int (*)(spl_store*);
+  auto copies = (CopiesFn)dlsym(RTLD_DEFAULT, "spl_hbm_vector_copies");
+  const int vc = copies && h.slots ? copies(spl_store_current()) : -1;
+  uint32_t gs = 0, gm = 0, stride = 0;
+  if (vc >= 0 && spl_store_geometry(spl_store_current(), &gs, &gm, &stride) == 0 && stride == 3200)
+    printf("vector_copies=fp32%s%s\n", (vc & 1) ? ",bf16" : "", (vc & 2) ? ",int8" : "");
   using ProbeFn = int (*)(spl_store*, spl_probe_stats*);
   auto probe = (ProbeFn)dlsym(RTLD_DEFAULT, "spl_hbm_probe_stats");
   spl_probe_stats ps{};

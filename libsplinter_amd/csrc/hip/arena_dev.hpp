@@ -60,6 +60,11 @@ struct Arena {
   __device__ __forceinline__ uint16_t* vec16(size_t i) const {
     return (uint16_t*)(side() + side_vec16_offset(slots)) + i * kEmbedDim;
   }
+  __device__ __forceinline__ bool has_vec8() const { return flags & SPL_ARENA_VEC8; }
+  __device__ __forceinline__ float2* q8meta() const { return (float2*)(side() + side_q8meta_offset(slots, flags)); }
+  __device__ __forceinline__ int8_t* vec8(size_t i) const {
+    return (int8_t*)(side() + side_vec8_offset(slots, flags)) + i * kEmbedDim;
+  }
 };
 
 // ---------------------------------------------------- bf16 vector copy ------
@@ -99,6 +104,104 @@ __device__ __forceinline__ void write_vec16_one(const Arena& a, size_t idx, cons
 // the slot holds no vector (fresh insert, unset, retrain): its norm 0 marks the copy dead
 __device__ __forceinline__ void clear_vec16(const Arena& a, size_t idx) {
   if (a.has_vec16()) a.nrm2()[idx] = 0.f;
+}
+
+// ---------------------------------------------------- int8 vector copy ------
+// The int8 copy of one slot's vector (SPL_ARENA_VEC8 arenas; states and layout: splinter_layout.hpp),
+// called where write_vec16_* / clear_vec16 are, under the slot's seqlock.  {rs, err} of a vector
+// with squared norm ss and largest magnitude m: returns the code scale 127 / m, 0 when the row
+// carries no codes (states {0, -1} and {0, 2}).
+__device__ __forceinline__ float q8_scale(float ss, float m, float* rs) {
+  *rs = 0.f;
+  if (!(ss > 2e-12f) || !(ss < __builtin_inff()) || !(m < __builtin_inff())) return 0.f;
+  *rs = m / (127.f * sqrtf(ss));
+  return 127.f / m;
+}
+// {0, -1}: no vector; {0, 2}: a vector the int8 pass cannot bound (norm at the exact kernel's floor,
+// or not finite)
+__device__ __forceinline__ float2 q8_dead(float ss) { return make_float2(0.f, ss == 0.f ? -1.f : 2.f); }
+__device__ __forceinline__ int q8_code(float x, float sc) {
+  return (int)fminf(fmaxf(rintf(x * sc), -127.f), 127.f);
+}
+// err: the fp32 error norm rounded up -- (1 + 2^-10) and 1e-6 cover the fp32 sums of 768 terms
+// (norm, error) and the roundings of x / |v| and c * rs
+__device__ __forceinline__ float q8_err(float es) { return sqrtf(es) * (1.f + 0.0009765625f) + 1e-6f; }
+
+// wave form: the lane layout of write_vec16_wave (lane l: dims 4 (l + 64 c) .. + 4, c = 0..2); three
+// coalesced 4-B stores per lane, lane 0 stores the meta entry
+__device__ __forceinline__ void write_vec8_wave(const Arena& a, size_t idx, const float4 (&v)[3], int lane) {
+  if (!a.has_vec8()) return;
+  float ss = 0.f, m = 0.f;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    ss += v[c].x * v[c].x + v[c].y * v[c].y + v[c].z * v[c].z + v[c].w * v[c].w;
+    m = fmaxf(m, fmaxf(fmaxf(fabsf(v[c].x), fabsf(v[c].y)), fmaxf(fabsf(v[c].z), fabsf(v[c].w))));
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    ss += __shfl_xor(ss, o, 64);
+    m = fmaxf(m, __shfl_xor(m, o, 64));
+  }
+  float rs;
+  const float sc = q8_scale(ss, m, &rs);
+  if (sc == 0.f) {  // wave-uniform
+    if (lane == 0) a.q8meta()[idx] = q8_dead(ss);
+    return;
+  }
+  const float inv = 1.f / sqrtf(ss);
+  uint32_t* d = (uint32_t*)a.vec8(idx);
+  float es = 0.f;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float x[4] = {v[c].x, v[c].y, v[c].z, v[c].w};
+    uint32_t w = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int q = q8_code(x[e], sc);
+      const float df = x[e] * inv - (float)q * rs;
+      es += df * df;
+      w |= (uint32_t)(q & 255) << (8 * e);
+    }
+    d[lane + 64 * c] = w;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) es += __shfl_xor(es, o, 64);
+  if (lane == 0) a.q8meta()[idx] = make_float2(rs, q8_err(es));
+}
+// one thread's form (the ring worker): the whole vector from `src` (768 floats)
+__device__ __forceinline__ void write_vec8_one(const Arena& a, size_t idx, const float* src) {
+  if (!a.has_vec8()) return;
+  float ss = 0.f, m = 0.f;
+  for (uint32_t c = 0; c < kEmbedDim; ++c) {
+    const float x = src[c];
+    ss += x * x;
+    m = fmaxf(m, fabsf(x));
+  }
+  float rs;
+  const float sc = q8_scale(ss, m, &rs);
+  if (sc == 0.f) {
+    a.q8meta()[idx] = q8_dead(ss);
+    return;
+  }
+  const float inv = 1.f / sqrtf(ss);
+  uint32_t* d = (uint32_t*)a.vec8(idx);
+  float es = 0.f;
+  for (uint32_t c = 0; c < kEmbedDim / 4; ++c) {
+    uint32_t w = 0;
+    for (int e = 0; e < 4; ++e) {
+      const float x = src[4 * c + e];
+      const int q = q8_code(x, sc);
+      const float df = x * inv - (float)q * rs;
+      es += df * df;
+      w |= (uint32_t)(q & 255) << (8 * e);
+    }
+    d[c] = w;
+  }
+  a.q8meta()[idx] = make_float2(rs, q8_err(es));
+}
+// the slot holds no vector (fresh insert, unset, retrain)
+__device__ __forceinline__ void clear_vec8(const Arena& a, size_t idx) {
+  if (a.has_vec8()) a.q8meta()[idx] = make_float2(0.f, -1.f);
 }
 
 // ------------------------------------------------------------- atomics --
@@ -660,6 +763,7 @@ __device__ __forceinline__ void write_meta(const Arena& a, const Claim& c, uint3
       uint4* ev = (uint4*)(s + kOffEmbed);
       for (uint32_t q = 0; q < kEmbedBytes / 16; ++q) st16<MO>(ev + q, make_uint4(0, 0, 0, 0));
       clear_vec16(a, (size_t)c.idx);
+      clear_vec8(a, (size_t)c.idx);
     }
   }
   ast32(s + kOffValLen, len);
@@ -690,6 +794,7 @@ __device__ __forceinline__ void write_set(const Arena& a, const Claim& c, const 
       uint4* ev = (uint4*)(s + kOffEmbed);
       for (uint32_t q = 0; q < kEmbedBytes / 16; ++q) st16<MO>(ev + q, make_uint4(0, 0, 0, 0));
       clear_vec16(a, (size_t)c.idx);
+      clear_vec8(a, (size_t)c.idx);
     }
   }
   ast32(s + kOffValLen, len);
@@ -841,6 +946,7 @@ __device__ int32_t unset_op(const Arena& a, const KeyT<KW>& k, long* out_idx) {
     uint4* ev = (uint4*)(s + kOffEmbed);
     for (uint32_t c = 0; c < kEmbedBytes / 16; ++c) ev[c] = make_uint4(0, 0, 0, 0);
     clear_vec16(a, (size_t)i);
+    clear_vec8(a, (size_t)i);
   }
   release();
   ast64(epoch_ptr(s), 2);  // reference contract: unset rewinds the epoch to 2
@@ -1025,6 +1131,7 @@ __device__ int32_t meta_apply(const Arena& a, const KeyT<KW>& k, int op, uint64_
       if (a.stride == kSlotEmbedBytes) {
         for (uint32_t c = 0; c < kEmbedBytes / 16; ++c) ((uint4*)(s + kOffEmbed))[c] = make_uint4(0, 0, 0, 0);
         clear_vec16(a, (size_t)idx);
+        clear_vec8(a, (size_t)idx);
       }
       release();
       ast64(epoch_ptr(s), 4);

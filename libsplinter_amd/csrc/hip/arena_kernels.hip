@@ -1331,6 +1331,7 @@ __global__ __launch_bounds__(kBlock) void k_embed_set(spl_arena_t aa, const char
         v[c] = __builtin_bit_cast(float4, x);
       }
       write_vec16_wave(a, (size_t)idx, v, lane);
+      write_vec8_wave(a, (size_t)idx, v, lane);
       release();
       __builtin_amdgcn_wave_barrier();
       if (lane == 0) {

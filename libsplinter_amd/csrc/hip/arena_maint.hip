@@ -20,6 +20,7 @@
 //                   become virgin slots, which splits the cluster.  Keys, values, vectors, the bf16
 //                   copy and the slot metadata move together; a slot's value row stays its own
 //                   (val_off is per position).  ONLINE: see "rehash" below for the protocol.
+//   k_vec8_rebuild  the side region's int8 copy + {scale, error bound} from the fp32 vectors (same)
 //   k_vec16_rebuild the side region's bf16 copy + squared norms from the fp32 vectors (after a
 //                   restore, or for an arena whose copy is missing).
 #include <hip/hip_runtime.h>
@@ -179,6 +180,10 @@ __device__ int move_online(const Arena& a, uint64_t q, uint64_t eq, uint64_t j, 
       copy16_wt((uint8_t*)a.vec16(q), (const uint8_t*)a.vec16(j), (uint32_t)kVec16Bytes, lane);
       if (lane == 0) a.nrm2()[q] = a.nrm2()[j];
     }
+    if (a.has_vec8()) {
+      copy16_wt((uint8_t*)a.vec8(q), (const uint8_t*)a.vec8(j), (uint32_t)kVec8Bytes, lane);
+      if (lane == 0) a.q8meta()[q] = a.q8meta()[j];
+    }
   }
   release();  // every lane's stores have left (the write-through ones and the plain tails)
   __builtin_amdgcn_wave_barrier();
@@ -197,6 +202,7 @@ __device__ int move_online(const Arena& a, uint64_t q, uint64_t eq, uint64_t j, 
     st16_wt(s + 16 * lane, v);
   }
   if (lane == 0 && a.has_vec16()) a.nrm2()[j] = 0.f;
+  if (lane == 0) clear_vec8(a, j);
   release();
   __builtin_amdgcn_wave_barrier();
   if (lane == 0) ast64(epoch_ptr(s), ej + 2);
@@ -404,6 +410,7 @@ struct RbGeom {
   uint32_t off_val;  // value row in the record
   uint32_t off_v16;  // bf16 vector (vec16 arenas)
   uint32_t off_n2;   // squared norm
+  uint32_t off_v8;   // int8 vector (vec8 arenas), then its {rs, err}
 };
 
 __global__ __launch_bounds__(256) void k_rb_collect(spl_arena_t aa, uint32_t* __restrict__ idx,
@@ -435,6 +442,10 @@ __global__ __launch_bounds__(256) void k_rb_gather(spl_arena_t aa, const uint32_
     if (a.has_vec16()) {
       copy16(r + g.off_v16, (const uint8_t*)a.vec16(i), kVec16Bytes, lane);
       if (lane == 0) *(float*)(r + g.off_n2) = a.nrm2()[i];
+    }
+    if (a.has_vec8()) {
+      copy16(r + g.off_v8, (const uint8_t*)a.vec8(i), kVec8Bytes, lane);
+      if (lane == 0) *(float2*)(r + g.off_v8 + kVec8Bytes) = a.q8meta()[i];
     }
   }
 }
@@ -479,6 +490,10 @@ __global__ __launch_bounds__(256) void k_rb_insert(spl_arena_t aa, const uint8_t
       copy16((uint8_t*)a.vec16((uint64_t)tgt), r + g.off_v16, kVec16Bytes, lane);
       if (lane == 0) a.nrm2()[tgt] = *(const float*)(r + g.off_n2);
     }
+    if (a.has_vec8()) {
+      copy16((uint8_t*)a.vec8((uint64_t)tgt), r + g.off_v8, kVec8Bytes, lane);
+      if (lane == 0) a.q8meta()[tgt] = *(const float2*)(r + g.off_v8 + kVec8Bytes);
+    }
     __builtin_amdgcn_wave_barrier();
     if (lane == 0) {
       *(uint32_t*)(d + kOffValOff) = voff;
@@ -506,6 +521,31 @@ __global__ __launch_bounds__(256) void k_vec16_rebuild(spl_arena_t aa) {
     for (int c = 0; c < 3; ++c) v[c] = src[lane + 64 * c];
     write_vec16_wave(a, i, v, lane);
   }
+}
+
+// one wave per slot: int8 copy + {rs, err} from the fp32 vector ({0, -1} for an empty slot)
+__global__ __launch_bounds__(256) void k_vec8_rebuild(spl_arena_t aa) {
+  const Arena a = from_api(aa);
+  const int lane = threadIdx.x & 63;
+  const uint64_t nw = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+  for (uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; i < a.slots; i += nw) {
+    const uint8_t* s = a.slot(i);
+    if (ald64(s + kOffHash) == 0) {
+      if (lane == 0) clear_vec8(a, i);
+      continue;
+    }
+    const float4* src = (const float4*)(s + kOffEmbed);
+    float4 v[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = src[lane + 64 * c];
+    write_vec8_wave(a, i, v, lane);
+  }
+}
+
+// every slot's int8 meta entry to "no vector" (a cleared slot array)
+__global__ __launch_bounds__(256) void k_vec8_clear(spl_arena_t aa) {
+  const Arena a = from_api(aa);
+  for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < a.slots; i += gridDim.x * 256ull) clear_vec8(a, i);
 }
 
 }  // namespace
@@ -549,6 +589,7 @@ int spl_arena_maint_mark(spl_arena_t a, int begin, int pid, uint64_t t0_ns, void
 uint32_t spl_arena_rebuild_rec(spl_arena_t a) {
   uint32_t rec = a.stride + ((a.max_val + 15) & ~15u);
   if (a.flags & SPL_ARENA_VEC16) rec += (uint32_t)kVec16Bytes + 16;
+  if (a.flags & SPL_ARENA_VEC8) rec += (uint32_t)kVec8Bytes + 16;
   return rec;
 }
 int spl_arena_rebuild_collect(spl_arena_t a, uint32_t* idx, void* count, hipStream_t s) {
@@ -562,6 +603,7 @@ int spl_arena_rebuild_move(spl_arena_t a, const uint32_t* idx, uint64_t n, void*
   g.off_val = a.stride;
   g.off_v16 = a.stride + ((a.max_val + 15) & ~15u);
   g.off_n2 = g.off_v16 + (uint32_t)kVec16Bytes;
+  g.off_v8 = g.off_v16 + ((a.flags & SPL_ARENA_VEC16) ? (uint32_t)kVec16Bytes + 16 : 0u);
   g.rec = spl_arena_rebuild_rec(a);
   const unsigned blocks = (unsigned)std::min<uint64_t>((n + 3) / 4 + 1, 16384);
   hipLaunchKernelGGL(k_rb_gather, dim3(blocks), dim3(256), 0, s, a, idx, n, (uint8_t*)tmp, g);
@@ -572,6 +614,10 @@ int spl_arena_rebuild_move(spl_arena_t a, const uint32_t* idx, uint64_t n, void*
   if (a.flags & SPL_ARENA_VEC16)
     (void)hipMemsetAsync((uint8_t*)a.base + side_offset(a.slots, a.stride, a.max_val) + side_nrm2_offset(), 0,
                          (size_t)a.slots * 4, s);
+  if (a.flags & SPL_ARENA_VEC8) {
+    long gc = ((long)a.slots + 255) / 256;
+    hipLaunchKernelGGL(k_vec8_clear, dim3((unsigned)(gc > 4096 ? 4096 : gc)), dim3(256), 0, s, a);
+  }
   if (spl_arena_init_slots(a, s) != 0) return (int)hipGetLastError();
   hipLaunchKernelGGL(k_rb_insert, dim3(blocks), dim3(256), 0, s, a, (const uint8_t*)tmp, n, g,
                      (unsigned long long*)fail);
@@ -584,6 +630,15 @@ int spl_arena_vec16_rebuild(spl_arena_t a, hipStream_t s) {
   if (g > 8192) g = 8192;
   if (g < 1) g = 1;
   hipLaunchKernelGGL(k_vec16_rebuild, dim3((unsigned)g), dim3(256), 0, s, a);
+  return (int)hipGetLastError();
+}
+
+int spl_arena_vec8_rebuild(spl_arena_t a, hipStream_t s) {
+  if (!a.base || !(a.flags & SPL_ARENA_VEC8) || a.stride != 3200) return (int)hipErrorInvalidValue;
+  long g = ((long)a.slots + 3) / 4;
+  if (g > 8192) g = 8192;
+  if (g < 1) g = 1;
+  hipLaunchKernelGGL(k_vec8_rebuild, dim3((unsigned)g), dim3(256), 0, s, a);
   return (int)hipGetLastError();
 }
 

@@ -62,7 +62,7 @@ struct HbmDescriptor {
   uint32_t mode;                         // 0 hipIpc, 1 VMM chunks (vmm_share.hpp)
   uint32_t nchunks;
   uint64_t chunk_bytes;
-  uint32_t side_flags;                   // SPL_ARENA_SIDE | SPL_ARENA_VEC16: the allocation's side region
+  uint32_t side_flags;                   // SPL_ARENA_SIDE | SPL_ARENA_VEC16 | SPL_ARENA_VEC8: the allocation's side region
   uint32_t pad2;
   char sock[96];                         // mode 1: abstract socket serving the chunk fds
   alignas(64) splinter_header control;  // host control plane (shard bids, event bus owner)
@@ -515,7 +515,10 @@ class HbmStore final : public StoreBase {
   int checkpoint(const char* path);
   long search_all(const float* q, uint64_t mask, float min_sim, float max_dist, long cap, spl_search_hit* out);
   long search_batch(const float* q, int nq, int k, float min_sim, float max_dist, uint64_t mask, spl_search_hit* out,
-                   int sample_div = 1, SearchSync* sync = nullptr);
+                   int sample_div = 1, SearchSync* sync = nullptr, bool allow8 = true);
+  // the operand the batched search would use on this store now (search_api.h spl_search_copy_kind)
+  int search_copy_kind() { return ensure_mapped() ? spl_search_copy_kind(arena()) : -1; }
+  uint32_t side_flags() const { return side_flags_; }
   int device() const { return device_; }
   struct SearchScratch;
   SearchScratch* ss_ = nullptr;
@@ -722,7 +725,7 @@ class HbmStore final : public StoreBase {
     return e && !strcmp(e, "0");
   }
   bool vmm_mode_ = false;
-  uint32_t side_flags_ = 0;  // SPL_ARENA_SIDE / SPL_ARENA_VEC16 of the allocation (descriptor)
+  uint32_t side_flags_ = 0;  // SPL_ARENA_SIDE / SPL_ARENA_VEC16 / SPL_ARENA_VEC8 of the allocation (descriptor)
   void* dbase_ = nullptr;  // raw_ + kAlignOffset (null until mapped: an opener attaches lazily)
   // Lazy attach: an opener whose per-call ops go to the owner's ring server maps the arena into its
   // own GPU address space only on the first op that needs it (batches, scans, search, raw pointers,
@@ -784,7 +787,7 @@ struct HbmStore::SearchScratch {
   void* res = nullptr;       // [256][32] CandRec
   void* scr = nullptr;       // exact kernel's lists
   uint16_t* qf = nullptr;    // [256][768] bf16 fragment operand
-  float* thr = nullptr;      // [256]
+  float* thr = nullptr;      // [256], then the int8 pass's query meta [256] float2
   float* bmax = nullptr;     // [sample tiles][256] (also the overflow flags)
   size_t bmax_bytes = 0;
   uint32_t* cnt = nullptr;   // [256][grid]
@@ -868,9 +871,12 @@ HbmStore* HbmStore::create(const char* name, size_t slots, size_t max_val, bool 
   // store the bf16 vector copy the batched search streams (SPLINTER_HBM_VEC16=0: none)
   const char* v16e = getenv("SPLINTER_HBM_VEC16");
   const bool vec16 = emb && !(v16e && !strcmp(v16e, "0"));
+  // ... and, opt-in, the int8 copy of the int8 candidate pass (SPLINTER_HBM_VEC8=1), with or without the bf16 one
+  const char* v8e = getenv("SPLINTER_HBM_VEC8");
+  const bool vec8 = emb && v8e && !strcmp(v8e, "1");
   const size_t side_off = side_offset(s->geo_.slots, s->geo_.stride, s->geo_.max_val);
-  const size_t alloc = side_off + side_bytes(s->geo_.slots, vec16) + 256;
-  s->side_flags_ = SPL_ARENA_SIDE | (vec16 ? SPL_ARENA_VEC16 : 0u);
+  s->side_flags_ = SPL_ARENA_SIDE | (vec16 ? SPL_ARENA_VEC16 : 0u) | (vec8 ? SPL_ARENA_VEC8 : 0u);
+  const size_t alloc = side_off + side_bytes(s->geo_.slots, s->side_flags_) + 256;
   // VMM chunks (attachable by other processes at any size), else one hipMalloc allocation
   const char* ve = getenv("SPLINTER_HBM_VMM");
   const size_t chunk_mb = getenv("SPLINTER_HBM_CHUNK_MB") ? (size_t)atol(getenv("SPLINTER_HBM_CHUNK_MB")) : 1024;
@@ -906,6 +912,7 @@ HbmStore* HbmStore::create(const char* name, size_t slots, size_t max_val, bool 
   (void)hipMemsetAsync((uint8_t*)s->dbase_ + side_off, 0,
                        vec16 ? side_vec16_offset(s->geo_.slots) : kSideHdrBytes, s->stream_);
   spl_arena_init_slots(s->arena(), s->stream_);
+  if (vec8) (void)spl_arena_vec8_rebuild(s->arena(), s->stream_);  // every slot empty: "no vector" entries
   (void)hipStreamSynchronize(s->stream_);
   HbmDescriptor* d = s->desc_;
   std::memcpy(&d->control, &h, sizeof h);
@@ -950,7 +957,7 @@ HbmStore* HbmStore::open(const char* name, int* err) {
   s->geo_.max_val = d->max_val;
   s->geo_.stride = d->stride;
   s->device_ = (int)d->device;
-  s->side_flags_ = d->side_flags & (SPL_ARENA_SIDE | SPL_ARENA_VEC16);
+  s->side_flags_ = d->side_flags & (SPL_ARENA_SIDE | SPL_ARENA_VEC16 | SPL_ARENA_VEC8);
   DevGuard dg(s->device_);
   if (d->version >= 3 && d->mode == 1) {
     std::vector<int> fds;
@@ -1110,7 +1117,8 @@ long HbmStore::search_all(const float* q, uint64_t mask, float min_sim, float ma
 // Batched top-k search of many queries (the C form of ops/search.py VectorSearch.search_batch, on the
 // MFMA passes of search_kernels.hip): per block of 256 queries a bf16 pass over a slot sample gives a
 // per-query candidate threshold (k-th largest per-tile maximum - 2 delta), a bf16 pass over the
-// whole arena (the side region's bf16 copy where the arena has one) emits the candidates above it,
+// whole arena (the side region's bf16 copy where the arena has one) emits the candidates above it
+// (an arena with the opt-in int8 copy: both passes on it, search_kernels.hip mf8, with a per-row bound),
 // and an fp32 re-score with the exact kernel's arithmetic ranks them; a query whose candidate
 // segment overflowed anywhere is redone with the exact kernel.  Results: out[q * k + j], ranked by
 // similarity desc, distance asc (reference splinter_cli_cmd_search.c:374-416); unused entries have
@@ -1140,7 +1148,7 @@ static hipStream_t search_stream(int device, int slot) {
 thread_local int g_search_slot = 0;
 
 long HbmStore::search_batch(const float* q, int nq, int k, float min_sim, float max_dist, uint64_t mask,
-                            spl_search_hit* out, int sample_div, SearchSync* sync) {
+                            spl_search_hit* out, int sample_div, SearchSync* sync, bool allow8) {
   if (!geo_.embeddings()) { errno = ENOTSUP; return -1; }
   if (nq <= 0 || k <= 0 || k > 32 || !q || !out) { errno = EINVAL; return -1; }
   if (!ensure_mapped()) return -1;
@@ -1167,7 +1175,7 @@ long HbmStore::search_batch(const float* q, int nq, int k, float min_sim, float 
          hipMallocAsync(&S.res, (size_t)kMmaQ * 32 * sizeof(CandRec), ss) == hipSuccess &&
          hipMallocAsync(&S.scr, (size_t)lists * kExactQ * 32 * sizeof(CandRec), ss) == hipSuccess &&
          hipMallocAsync((void**)&S.qf, (size_t)kMmaQ * kEmbedDim * 2, ss) == hipSuccess &&
-         hipMallocAsync((void**)&S.thr, (size_t)kMmaQ * 4, ss) == hipSuccess &&
+         hipMallocAsync((void**)&S.thr, (size_t)kMmaQ * (4 + 8), ss) == hipSuccess &&
          hipMallocAsync((void**)&S.cnt, (size_t)kMmaQ * kMmaGrid * 4, ss) == hipSuccess &&
          hipMallocAsync((void**)&S.cand, (size_t)kMmaQ * kMmaGrid * kCapb * 4, ss) == hipSuccess &&
          hipMallocAsync(&S.cores, (size_t)kMmaQ * 32 * 128, ss) == hipSuccess &&
@@ -1207,45 +1215,56 @@ long HbmStore::search_batch(const float* q, int nq, int k, float min_sim, float 
   // query would overflow its segments and be redone alone): those batches go to the exact kernel
   // directly, kExactQ queries per arena scan
   const bool exact_only = !mma || (bounded && min_sim <= -1.f);
+  // the int8 candidate pass where the arena carries the copy (a node search: where every shard
+  // does, so the merged samples mean one thing): its sampled maxima are lower bounds of real
+  // similarities already, so no margin comes off the k-th largest (delta2 = 0), and the floor
+  // keeps only the allowance against the exact kernel's fp32 cosine
+  const bool i8 = allow8 && spl_search_copy_kind(a) == SPL_SEARCH_COPY_INT8;
+  const float delta2 = i8 ? 0.f : 2 * kDelta;
+  void* qmeta = S.thr ? (void*)(S.thr + kMmaQ) : nullptr;
+  auto pass = [&](int n, long end, int mode, float* bmax, uint32_t* cnt, uint32_t* cand, int capb) {
+    const float* thr = mode ? S.thr : nullptr;
+    return i8 ? spl_search_mma_pass8(a, S.qf, qmeta, n, 0, end, mask, mode, thr, bmax, cnt, cand, capb, kMmaGrid, ss)
+              : spl_search_mma_pass(a, S.qf, n, 0, end, mask, mode, thr, bmax, cnt, cand, capb, kMmaGrid, ss);
+  };
   for (int b = 0; ok && b < nq; b += kMmaQ) {  // (a shard that fails leaves the node's threshold merge)
     const int n = std::min(kMmaQ, nq - b);
     const float* hq = q + (size_t)b * kEmbedDim;
-    const float floor_v = min_sim - kDelta;
+    const float floor_v = min_sim - (i8 ? 4e-4f : kDelta);
     if (exact_only) {
       if (sync) {  // a shard on the exact kernel still takes part in the block's threshold merge
         thr_h.assign((size_t)n, floor_v);
-        sync->merge(nullptr, n, k, 2 * kDelta, floor_v, thr_h.data());
+        sync->merge(nullptr, n, k, delta2, floor_v, thr_h.data());
       }
       ok = exact(hq, n, res.data() + (size_t)b * k, cores.data() + (size_t)b * k * 128);
       continue;
     }
-    // queries up once (fp32); the bf16 fragment operand is built on the device (spl_search_qprep)
+    // queries up once (fp32); the bf16 / int8 fragment operand is built on the device (spl_search_qprep[8])
     std::memcpy(S.hq(), hq, (size_t)n * kEmbedBytes);
     ok = hipMemcpyAsync(S.q, S.hq(), (size_t)n * kEmbedBytes, hipMemcpyHostToDevice, ss) == hipSuccess &&
-         spl_search_qprep(S.q, n, S.qf, ss) == 0;
+         (i8 ? spl_search_qprep8(S.q, n, S.qf, qmeta, ss) : spl_search_qprep(S.q, n, S.qf, ss)) == 0;
     if (ok && !bounded) {
       // node search: the k largest sampled maxima per query come back (staged in S.cnt, which the
       // candidate pass clears afterwards) for the shards' union threshold
       float* topv_d = sync ? (float*)S.cnt : nullptr;
-      ok = spl_search_mma_pass(a, S.qf, n, 0, sample, mask, 0, nullptr, S.bmax, nullptr, nullptr, 0, kMmaGrid, ss) ==
-               0 &&
-           spl_search_thr_topk(S.bmax, (int)(sample / kMmaTile), n, k, 2 * kDelta, floor_v, S.thr, topv_d, ss) == 0;
+      ok = pass(n, sample, 0, S.bmax, nullptr, nullptr, 0) == 0 &&
+           spl_search_thr_topk(S.bmax, (int)(sample / kMmaTile), n, k, delta2, floor_v, S.thr, topv_d, ss) == 0;
       if (sync) {
         float* tv = (float*)S.hres();  // pinned staging, free until the results come back
         const bool got = ok && hipMemcpyAsync(tv, topv_d, (size_t)n * k * 4, hipMemcpyDeviceToHost, ss) == hipSuccess &&
                          hipStreamSynchronize(ss) == hipSuccess;
         float* th = (float*)S.hover();
-        sync->merge(got ? tv : nullptr, n, k, 2 * kDelta, floor_v, th);
+        sync->merge(got ? tv : nullptr, n, k, delta2, floor_v, th);
         ok = got && hipMemcpyAsync(S.thr, th, (size_t)n * 4, hipMemcpyHostToDevice, ss) == hipSuccess;
       }
     } else {
       thr_h.assign((size_t)n, floor_v);
-      if (sync) sync->merge(nullptr, n, k, 2 * kDelta, floor_v, thr_h.data());
+      if (sync) sync->merge(nullptr, n, k, delta2, floor_v, thr_h.data());
       ok = ok && hipMemcpyAsync(S.thr, thr_h.data(), (size_t)n * 4, hipMemcpyHostToDevice, ss) == hipSuccess;
     }
     // (the overflow flags reuse S.bmax: the threshold is built by then)
     ok = ok && hipMemsetAsync(S.cnt, 0, (size_t)n * kMmaGrid * 4, ss) == hipSuccess &&
-         spl_search_mma_pass(a, S.qf, n, 0, slots, mask, 1, S.thr, nullptr, S.cnt, S.cand, kCapb, kMmaGrid, ss) == 0 &&
+         pass(n, slots, 1, nullptr, S.cnt, S.cand, kCapb) == 0 &&
          spl_search_rescore(a, S.q, n, k, min_sim, max_dist, mask, S.cnt, S.cand, kMmaGrid, kCapb, S.res, ss) == 0 &&
          spl_search_overflow(S.cnt, n, kMmaGrid, kCapb, (uint32_t*)S.bmax, ss) == 0 &&
          spl_search_cores(a, S.res, n * k, S.cores, ss) == 0;
@@ -1362,6 +1381,10 @@ int HbmStore::restore_from(const char* path) {
   if (rc == 0 && (side_flags_ & SPL_ARENA_VEC16)) {
     std::lock_guard<std::mutex> lk(mu_);
     if (spl_arena_vec16_rebuild(arena(), stream_) != 0 || hipStreamSynchronize(stream_) != hipSuccess) rc = -1;
+  }
+  if (rc == 0 && (side_flags_ & SPL_ARENA_VEC8)) {  // ... and the int8 copy
+    std::lock_guard<std::mutex> lk(mu_);
+    if (spl_arena_vec8_rebuild(arena(), stream_) != 0 || hipStreamSynchronize(stream_) != hipSuccess) rc = -1;
   }
   return rc;
 }
@@ -1888,13 +1911,21 @@ long spl_search_batch(spl_store* h, const float* queries, int nq, int k, float m
         if (sj && sj->device() == si->device()) ++slot[(size_t)i];
       }
     }
+    // one decision per call, before the fan-out: the int8 pass only when every shard has the copy
+    // (its sampled maxima are lower bounds, the bf16 pass's are approximations: the threshold
+    // merge takes values of one meaning)
+    bool all8 = true;
+    for (int i = 0; i < n; ++i) {
+      auto* si = dynamic_cast<spl::HbmStore*>((spl::StoreBase*)spl_node_shard(h, i));
+      all8 = all8 && si && si->search_copy_kind() == SPL_SEARCH_COPY_INT8;
+    }
     spl::SearchSync sync(n);
     for (int i = 0; i < n; ++i)
       th.emplace_back([&, i] {
         spl::g_search_slot = slot[(size_t)i];
         auto* s = dynamic_cast<spl::HbmStore*>((spl::StoreBase*)spl_node_shard(h, i));
         rc[(size_t)i] =
-            s ? s->search_batch(queries, nq, k, min_sim, max_dist, mask, part[(size_t)i].data(), n, &sync) : -1;
+            s ? s->search_batch(queries, nq, k, min_sim, max_dist, mask, part[(size_t)i].data(), n, &sync, all8) : -1;
         sync.leave();
       });
     for (auto& t : th) t.join();
@@ -1924,6 +1955,26 @@ long spl_search_batch(spl_store* h, const float* queries, int nq, int k, float m
     }
   }
   return nq;
+}
+
+// Vector copies an HBM store's arena carries beside the fp32 rows: bit 0 the bf16 copy, bit 1 the
+// int8 copy; a node store: the copies every shard carries (what a node search can use).  < 0: not
+// an HBM / node-of-HBM store.
+int spl_hbm_vector_copies(spl_store* h) {
+  if (!h) return -2;
+  auto bits = [](spl::HbmStore* s) {
+    return ((s->side_flags() & SPL_ARENA_VEC16) ? 1 : 0) | ((s->side_flags() & SPL_ARENA_VEC8) ? 2 : 0);
+  };
+  if (auto* s = dynamic_cast<spl::HbmStore*>((spl::StoreBase*)h)) return bits(s);
+  const int n = spl_node_nshards(h);
+  if (n < 1) return -2;
+  int all = 3;
+  for (int i = 0; i < n; ++i) {
+    auto* s = dynamic_cast<spl::HbmStore*>((spl::StoreBase*)spl_node_shard(h, i));
+    if (!s) return -1;
+    all &= bits(s);
+  }
+  return all;
 }
 
 // Probe-chain statistics of an HBM store, or summed over the shards of a node store (maxima taken)

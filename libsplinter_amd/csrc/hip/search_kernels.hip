@@ -678,6 +678,234 @@ __global__ __launch_bounds__(kThreads, 1) void k_search_mma16(spl_arena_t aa, co
 }
 }  // namespace mf16
 
+// ---------------------------------------------------------------------------
+// The candidate pass on the side region's int8 copy (SPL_ARENA_VEC8 arenas, splinter_layout.hpp):
+// 768 B per slot, half the bf16 copy's bytes, on v_mfma_i32_16x16x64_i8.  A K-chunk of 64 dims is
+// 64 B per row, the byte geometry of mf16 (16-B fragment per lane over a 64-B row piece): the ring,
+// the DMA addressing and the rsw swizzle are mf16's, with 12 K-steps per tile instead of 24.  Lane
+// (fr, fq) holds bytes [16 fq, +16) of its row piece / query piece as the A / B fragment: both
+// operands put the same dims in the same lane group and byte, so the sum over k pairs them
+// whatever order the instruction walks k in.  The integer dot product is exact (|acc| <= 768 * 127^2
+// < 2^24, exact in fp32 too).
+// With unit vectors q^, v^ and their dequantised forms q~ = cq qs, v~ = cv rs:
+//   |q^.v^ - q~.v~| <= |v^ - v~| + |q^ - q~| |v~| <= err + eq (1 + err),
+// so with approx = float(acc) rs qs and B = err + eq (1 + err) + 4e-4 + 2e-6 (4e-4: the real cosine
+// against the exact kernel's fp32 cosine, the last term of ops/search.py DELTA; 2e-6: the fp32
+// roundings of this epilogue) the exact kernel's cosine lies in [approx - B, approx + B].
+//   MODE 0: per-tile maximum of approx - B over the live rows with codes (rs > 0): a lower bound
+//           of a real similarity, so the k-th largest tile maximum is the threshold itself;
+//   MODE 1: a live row is a candidate when approx + B >= thr[q], or when its vector cannot be
+//           bounded (err >= 2); rows without a vector (err < 0) never are.
+// In-order vmcnt: a wave issues per step (the metadata -- hash, bloom, the 8-B q8meta entry: 3
+// loads -- at step 0, then) the DMA of chunk s + 3, 2 query + 2 row pieces = 4.  Chunk s's DMA is
+// the last op of step s - 3 (for s < 3: of step s + 9 of the tile before, or of the prologue, which
+// issues chunks 0, 1, 2 back to back); younger than it at the top of step s are the two steps
+// between, 4 + 4 = 8, plus the 3 metadata loads when one of the two was a step 0 (s = 1, 2): 11.
+// In the first tile s = 0 has chunks 1, 2 behind chunk 0 (8), s = 1 has chunk 2 and step 0 (4 + 3 +
+// 4 = 11), s = 2 has steps 0 and 1 (3 + 4 + 4 = 11): the same counts.
+namespace mf8 {
+using mf::f32x4;
+using mf::rsrc_t;
+using mf::lds_void;
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+constexpr int kTile = mf::kTile, kQ = mf::kQ, kNJ = mf::kNJ;
+constexpr int kSteps = kD / 64;           // 12 K-chunks of 64 dims per tile
+constexpr int kWaves = 8, kThreads = kWaves * 64;  // two waves per SIMD
+constexpr int kChunk = kTile * 64;        // 16 KB of int8 slot rows per K-chunk
+constexpr int kQChunk = kQ * 64;          // 16 KB of int8 query fragments per K-chunk
+constexpr int kRing = mf::kRing, kAhead = mf::kAhead;
+constexpr int kRows = kTile / kWaves;     // slot rows a wave stages (DMA, metadata): 32
+constexpr int kBlk = 8;                   // 16-row blocks per wave: one slot half
+constexpr int kRsrcWord3 = mf::kRsrcWord3;
+constexpr float kSlack = 4e-4f + 2e-6f;
+static_assert(kSteps % kRing == 0 && kSteps > kAhead, "static ring slots across tiles");
+struct Smem {
+  char ring[kRing][kChunk];   // 64 KB
+  char qring[kRing][kQChunk]; // 64 KB
+  __attribute__((aligned(16))) float rs[kTile];
+  __attribute__((aligned(16))) float er[kTile];  // err of a live row, -1 for a row that does not count
+  uint32_t ncand[kQ];
+  float pmax[kQ];             // MODE 0: the upper slot half's per-query maxima
+  float2 qm[kQ];              // {qs, eq} per query, and MODE 1's thresholds: read in the epilogue only, so
+  float thr[kQ];              // they hold no registers across the K loop
+};
+using mf16::rsw;
+
+__device__ __forceinline__ rsrc_t tile_rsrc8(const spl::dev::Arena& a, long t, long slot_end) {
+  return __builtin_amdgcn_make_buffer_rsrc(a.vec8((size_t)mf::tile_start(t, slot_end)), 0, kTile * kD, kRsrcWord3);
+}
+
+template <int MODE>
+__global__ __launch_bounds__(kThreads, 1) void k_search_mma8(spl_arena_t aa, const void* __restrict__ qf,
+                                                            const float2* __restrict__ qmeta, int nq, long slot_begin,
+                                                            long slot_end, uint64_t mask,
+                                                            const float* __restrict__ thr_in, float* __restrict__ bmax,
+                                                            uint32_t* __restrict__ cnt, uint32_t* __restrict__ cand,
+                                                            int capb) {
+  __shared__ __attribute__((aligned(16))) Smem sm;
+  const spl::dev::Arena a = spl::dev::from_api(aa);
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int fr = lane & 15, fq = lane >> 4;
+  const int qg = wave & 3, sh = wave >> 2;
+  const long tile_base = slot_begin / kTile;
+  const long tile_end = (slot_end + kTile - 1) / kTile, G = gridDim.x;
+  const long t0 = tile_base + blockIdx.x;
+  if (t0 >= tile_end) return;  // block-uniform
+  if (MODE == 1 && tid < kQ) sm.ncand[tid] = 0;
+
+  const rsrc_t qr = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(qf), 0, kQ * kD, kRsrcWord3);
+  const int qtile0 = qg * kNJ;
+  // row DMA: wave-instruction k of a chunk fills rows 32w + 16k .. +16 (1 KB), lane l -> row +(l >> 2),
+  // physical unit l & 3 <- logical unit (l & 3) ^ rsw(row & 15); query DMA: instruction k brings the
+  // 1-KB fragment block of 16-query tile 2w + k for the chunk's step (lane-linear, as read)
+  int dvoff[2];
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const int row = wave * kRows + k * 16 + (lane >> 2);
+    dvoff[k] = row * kD + (((lane & 3) ^ rsw(row & 15)) << 4);
+  }
+  const float2* q8m = a.q8meta();
+  // fragment read: row 16i + fr of this wave's slot half, logical unit fq
+  const int rdo = fr * 64 + ((fq ^ rsw(fr)) << 4) + sh * kBlk * 1024;
+
+  if (tid < kQ) {
+    sm.qm[tid] = qmeta[tid];
+    sm.thr[tid] = (MODE == 1 && tid < nq) ? thr_in[tid] : FLT_MAX;
+  }
+  auto issue = [&](rsrc_t er, int c, int slot) {
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(qr, (lds_void*)(sm.qring[slot] + (2 * wave + k) * 1024), 16, lane * 16,
+                                               ((2 * wave + k) * kSteps + c) * 1024, 0, 0);
+    char* dst = sm.ring[slot] + wave * kRows * 64;
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(er, (lds_void*)(dst + k * 1024), 16, dvoff[k], c * 64, 0, 0);
+  };
+  const long last = tile_end - 1;
+  // (visible to every wave after the first step's barrier; the epilogue reads them many barriers later)
+  {
+    const rsrc_t er = tile_rsrc8(a, t0, slot_end);
+    for (int c = 0; c < kAhead; ++c) issue(er, c, c);
+  }
+
+  for (long t = t0; t < tile_end; t += G) {
+    const long start = mf::tile_start(t, slot_end);
+    const rsrc_t er_cur = tile_rsrc8(a, t, slot_end);
+    const rsrc_t er_next = tile_rsrc8(a, t + G < tile_end ? t + G : last, slot_end);
+    uint64_t h = 0, bl = 0;
+    float2 rm = make_float2(0.f, -1.f);
+    i32x4 acc[kBlk][kNJ];
+#pragma unroll
+    for (int i = 0; i < kBlk; ++i)
+#pragma unroll
+      for (int j = 0; j < kNJ; ++j) acc[i][j] = i32x4{0, 0, 0, 0};
+
+#pragma clang loop unroll(full)
+    for (int s = 0; s < kSteps; ++s) {
+      if (s == 1 || s == 2)
+        SPL_STEP_SYNC(11);
+      else
+        SPL_STEP_SYNC(8);
+      if (s == 0) {  // metadata of this wave's 32 rows (lanes 32-63 repeat 0-31)
+        const long row = start + wave * kRows + (lane & (kRows - 1));
+        const uint8_t* sp = a.slot((size_t)row);
+        h = __builtin_nontemporal_load((const uint64_t*)(sp + spl::kOffHash));
+        bl = __builtin_nontemporal_load((const uint64_t*)(sp + spl::kOffBloom));
+        const uint64_t mw = __builtin_nontemporal_load((const uint64_t*)(q8m + row));
+        rm = make_float2(__builtin_bit_cast(float, (uint32_t)mw), __builtin_bit_cast(float, (uint32_t)(mw >> 32)));
+      }
+      const char* qsp = sm.qring[s % kRing] + lane * 16;
+      i32x4 bq[kNJ];
+#pragma unroll
+      for (int j = 0; j < kNJ; ++j) bq[j] = *(const i32x4*)(qsp + (qtile0 + j) * 1024);
+      const char* ch = sm.ring[s % kRing] + rdo;
+#pragma unroll
+      for (int i0 = 0; i0 < kBlk; i0 += 4) {
+        i32x4 af[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) af[u] = *(const i32x4*)(ch + (i0 + u) * 1024);
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+          for (int j = 0; j < kNJ; ++j)
+            acc[i0 + u][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[u], bq[j], acc[i0 + u][j], 0, 0, 0);
+        // the next chunk's DMA after the first MFMA group, as in mf16
+        if (i0 == 0) issue(s + kAhead < kSteps ? er_cur : er_next, (s + kAhead) % kSteps, (s + kAhead) % kRing);
+      }
+    }
+    {
+      const int row = wave * kRows + lane;
+      if (lane < kRows) {
+        const bool live = h != 0 && (!mask || (bl & mask) == mask) && start + row >= t * kTile && rm.y >= 0.f;
+        sm.rs[row] = rm.x;
+        sm.er[row] = live ? rm.y : -1.f;
+      }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    {
+      const f32x4* rsp = (const f32x4*)(sm.rs + fq * 4 + sh * kBlk * 16);  // rows 16i + 4fq + r, r = 0..3
+      const f32x4* erp = (const f32x4*)(sm.er + fq * 4 + sh * kBlk * 16);
+      float best[kNJ], thr[kNJ], qs[kNJ], eq[kNJ];
+#pragma unroll
+      for (int j = 0; j < kNJ; ++j) {
+        const int q = (qtile0 + j) * 16 + fr;
+        best[j] = -FLT_MAX;
+        thr[j] = sm.thr[q];
+        qs[j] = sm.qm[q].x;
+        eq[j] = sm.qm[q].y;
+      }
+#pragma unroll
+      for (int i = 0; i < kBlk; ++i) {
+        const f32x4 rv = rsp[i * 4];
+        const f32x4 ev = erp[i * 4];
+#pragma unroll
+        for (int j = 0; j < kNJ; ++j)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float approx = (float)acc[i][j][r] * rv[r] * qs[j];
+            const float B = ev[r] + eq[j] * (1.f + ev[r]) + kSlack;
+            if (MODE == 0) {
+              if (ev[r] >= 0.f && rv[r] > 0.f) best[j] = fmaxf(best[j], approx - B);
+            } else if (ev[r] >= 0.f && (approx + B >= thr[j] || ev[r] >= 2.f)) {
+              const int q = (qtile0 + j) * 16 + fr;
+              if (q < nq) {
+                const uint32_t p = atomicAdd(&sm.ncand[q], 1u);
+                if (p < (uint32_t)capb)
+                  cand[((long)q * gridDim.x + blockIdx.x) * capb + p] = (uint32_t)(start + (sh * kBlk + i) * 16 + fq * 4 + r);
+              }
+            }
+          }
+      }
+      if (MODE == 0) {  // per query: max over the lane quads, then the two slot halves meet in LDS
+        float bj[kNJ];
+#pragma unroll
+        for (int j = 0; j < kNJ; ++j) {
+          bj[j] = fmaxf(best[j], __shfl_xor(best[j], 16, 64));
+          bj[j] = fmaxf(bj[j], __shfl_xor(bj[j], 32, 64));
+        }
+        if (sh == 1 && fq == 0)
+#pragma unroll
+          for (int j = 0; j < kNJ; ++j) sm.pmax[(qtile0 + j) * 16 + fr] = bj[j];
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        if (sh == 0 && fq == 0)
+#pragma unroll
+          for (int j = 0; j < kNJ; ++j) {
+            const int q = (qtile0 + j) * 16 + fr;
+            if (q < nq) bmax[(t - tile_base) * nq + q] = fmaxf(bj[j], sm.pmax[q]);
+          }
+      }
+    }
+  }
+  if (MODE == 1) {
+    mf::raw_barrier();
+    const int q = threadIdx.x;
+    if (q < nq && q < kQ) cnt[(long)q * gridDim.x + blockIdx.x] = sm.ncand[q];
+  }
+  mf::wait_vm0();
+}
+}  // namespace mf8
+
 namespace mf {
 // fp32 re-score of the candidates of one query (block) and top-K selection;
 // same arithmetic as k_score_topk so the ranking is identical.  Candidates
@@ -888,6 +1116,57 @@ __global__ __launch_bounds__(256) void k_search_qprep(const float* __restrict__ 
   }
 }
 
+// The int8 candidate pass's query operand: one workgroup per query slot of the 256-query block --
+// the codes c = rint(q 127 / max|q|) in fragment order [16 q-tiles][12 steps][4 kq][16 r][16 B]
+// (dims [64 step + 16 kq, +16) of query 16 tile + r) and qmeta {qs, eq}, defined as the rows'
+// {rs, err} (arena_dev.hpp write_vec8_wave).  Query slots >= n: zeros and {0, -1}; a query without
+// a usable norm (zero, not finite): zeros and {0, 2} -- every live row becomes its candidate and
+// the exact kernel answers it.
+__global__ __launch_bounds__(256) void k_search_qprep8(const float* __restrict__ q, int n, int8_t* __restrict__ qf,
+                                                       float2* __restrict__ qmeta) {
+  using namespace spl::dev;
+  const int qi = blockIdx.x, t = threadIdx.x;
+  __shared__ float red[3][4];
+  float v[3] = {0.f, 0.f, 0.f};
+  if (qi < n) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = q[(long)qi * 768 + t + 256 * c];
+  }
+  float ss = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
+  float m = fmaxf(fabsf(v[0]), fmaxf(fabsf(v[1]), fabsf(v[2])));
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    ss += __shfl_xor(ss, o, 64);
+    m = fmaxf(m, __shfl_xor(m, o, 64));
+  }
+  if ((t & 63) == 0) { red[0][t >> 6] = ss; red[1][t >> 6] = m; }
+  __syncthreads();
+  ss = red[0][0] + red[0][1] + red[0][2] + red[0][3];
+  m = fmaxf(fmaxf(red[1][0], red[1][1]), fmaxf(red[1][2], red[1][3]));
+  float qsv = 0.f;
+  const float sc = qi < n ? q8_scale(ss, m, &qsv) : 0.f;
+  const float inv = sc != 0.f ? 1.f / sqrtf(ss) : 0.f;
+  const int tile = qi >> 4, r = qi & 15;
+  float es = 0.f;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const int d = t + 256 * c;
+    const int st = d >> 6, kq = (d >> 4) & 3, e = d & 15;
+    const int code = sc != 0.f ? q8_code(v[c], sc) : 0;
+    const float df = v[c] * inv - (float)code * qsv;
+    es += sc != 0.f ? df * df : 0.f;
+    qf[((((long)tile * 12 + st) * 4 + kq) * 16 + r) * 16 + e] = (int8_t)code;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) es += __shfl_xor(es, o, 64);
+  if ((t & 63) == 0) red[2][t >> 6] = es;
+  __syncthreads();
+  if (t == 0) {
+    es = red[2][0] + red[2][1] + red[2][2] + red[2][3];
+    qmeta[qi] = qi >= n ? make_float2(0.f, -1.f) : sc != 0.f ? make_float2(qsv, q8_err(es)) : make_float2(0.f, 2.f);
+  }
+}
+
 // slot cores (128 B) of a result list, gathered on the device so the hits leave with their keys
 // in the same copy: res[n] Cand -> out[n][128] (zeros for an empty entry).  8 lanes per entry.
 __global__ __launch_bounds__(256) void k_search_cores(spl_arena_t aa, const Cand* __restrict__ res, int n,
@@ -933,6 +1212,44 @@ int spl_search_lists(int grid) { return grid * kWaves; }
 int spl_search_qprep(const float* queries, int nq, void* qfrag, hipStream_t s) {
   if (nq <= 0 || nq > mf::kQ || !queries || !qfrag) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(k_search_qprep, dim3(mf::kQ), dim3(256), 0, s, queries, nq, (uint16_t*)qfrag);
+  return (int)hipGetLastError();
+}
+
+int spl_search_qprep8(const float* queries, int nq, void* qfrag8, void* qmeta, hipStream_t s) {
+  if (nq <= 0 || nq > mf::kQ || !queries || !qfrag8 || !qmeta) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_search_qprep8, dim3(mf::kQ), dim3(256), 0, s, queries, nq, (int8_t*)qfrag8, (float2*)qmeta);
+  return (int)hipGetLastError();
+}
+
+// which operand the batched search uses on this arena (search_api.h); the environment is read per
+// call so that one process can compare the paths
+int spl_search_copy_kind(spl_arena_t a) {
+  if (a.stride != 3200) return SPL_SEARCH_COPY_FP32;
+  const char* e8 = getenv("SPLINTER_SEARCH_VEC8");
+  if ((a.flags & SPL_ARENA_VEC8) && !(e8 && e8[0] == '0')) return SPL_SEARCH_COPY_INT8;
+  const char* e16 = getenv("SPLINTER_SEARCH_VEC16");
+  if ((a.flags & SPL_ARENA_VEC16) && !(e16 && e16[0] == '0')) return SPL_SEARCH_COPY_BF16;
+  return SPL_SEARCH_COPY_FP32;
+}
+
+int spl_search_mma_pass8(spl_arena_t a, const void* qfrag8, const void* qmeta, int nq, long slot_begin, long slot_end,
+                         uint64_t mask, int mode, const float* thr, float* bmax, uint32_t* cnt, uint32_t* cand,
+                         int capb, int grid, hipStream_t s) {
+  if (a.stride != 3200 || !(a.flags & SPL_ARENA_VEC8) || !qfrag8 || !qmeta || nq <= 0 || nq > mf::kQ ||
+      slot_begin < 0 || slot_begin % mf::kTile || slot_end > (long)a.slots || slot_end - slot_begin < mf::kTile ||
+      (mode != 0 && mode != 1) || grid <= 0 || (mode == 1 && (!thr || !cnt || !cand || capb <= 0)) ||
+      (mode == 0 && !bmax))
+    return (int)hipErrorInvalidValue;
+  const long tiles = (slot_end - slot_begin + mf::kTile - 1) / mf::kTile;
+  if (mode == 0) {
+    const int g = (int)(grid < tiles ? grid : tiles);
+    hipLaunchKernelGGL(mf8::k_search_mma8<0>, dim3(g), dim3(mf8::kThreads), 0, s, a, qfrag8, (const float2*)qmeta, nq,
+                       slot_begin, slot_end, mask, thr, bmax, cnt, cand, capb);
+  } else {
+    // every one of the `grid` segments per query is read: blocks without a tile leave the zeroed count
+    hipLaunchKernelGGL(mf8::k_search_mma8<1>, dim3(grid), dim3(mf8::kThreads), 0, s, a, qfrag8, (const float2*)qmeta, nq,
+                       slot_begin, slot_end, mask, thr, bmax, cnt, cand, capb);
+  }
   return (int)hipGetLastError();
 }
 

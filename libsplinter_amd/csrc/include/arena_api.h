@@ -29,6 +29,8 @@ typedef struct spl_arena {
 #define SPL_ARENA_EVENTBUS 1u  /* event bus armed (maintain the dirty mask) */
 #define SPL_ARENA_SIDE     2u  /* the allocation carries the side region (splinter_layout.hpp) */
 #define SPL_ARENA_VEC16    4u  /* ... with the bf16 vector copy + squared norms (embedding stores) */
+#define SPL_ARENA_VEC8     8u  /* ... with the int8 vector copy + {scale, error bound} per row (opt-in,
+                                  independent of SPL_ARENA_VEC16: an arena may carry both or one) */
 
 #ifndef __HIP_PLATFORM_AMD__
 typedef void *hipStream_t;
@@ -97,6 +99,9 @@ int spl_arena_rehash(spl_arena_t a, void *counters, hipStream_t stream);
  * ok: device u64, 1 when the open won (no other pass was running) */
 int spl_arena_maint_mark(spl_arena_t a, int begin, int pid, uint64_t t0_ns, void *ok, hipStream_t stream);
 int spl_arena_vec16_rebuild(spl_arena_t a, hipStream_t stream);
+/* the int8 vector copy and its per-row {scale, error bound} rebuilt from the fp32 vectors
+ * (SPL_ARENA_VEC8 arenas); empty slots get the "no vector" state */
+int spl_arena_vec8_rebuild(spl_arena_t a, hipStream_t stream);
 /* full rebuild (exclusive): collect the live slot indices (device u32[slots], count: device u64
  * zeroed), then move them out to tmp (n * spl_arena_rebuild_rec bytes), clear the slot array and
  * re-insert every entry (fail: device u64 zeroed, entries left without a slot: 0 when n <= slots) */

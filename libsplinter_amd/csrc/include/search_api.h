@@ -32,6 +32,29 @@ int spl_search_mma_pass(spl_arena_t a, const void *qfrag, int nq, long slot_begi
 /* queries [nq <= 256, 768] fp32 (device) -> qfrag as spl_search_mma_pass takes it (normalised,
  * bf16, zero-padded to 256 queries, fragment order) */
 int spl_search_qprep(const float *queries, int nq, void *qfrag, hipStream_t stream);
+
+/* The int8 candidate pass (SPL_ARENA_VEC8 arenas, splinter_layout.hpp).  spl_search_copy_kind: the
+ * operand the batched search should use on this arena now -- the int8 copy when the arena has one
+ * (SPLINTER_SEARCH_VEC8=0, read per call: ignore it), else the bf16 copy (SPLINTER_SEARCH_VEC16=0:
+ * ignore it), else the fp32 rows.  Hosts pick the query operand and the threshold margin by it. */
+#define SPL_SEARCH_COPY_FP32 0
+#define SPL_SEARCH_COPY_BF16 1
+#define SPL_SEARCH_COPY_INT8 2
+int spl_search_copy_kind(spl_arena_t a);
+/* queries [nq <= 256, 768] fp32 (device) -> qfrag8: int8 codes c = rint(q 127 / max|q|) of each
+ * query, zero-padded to 256 queries, in fragment order [16 tiles][12 steps][64 lanes] x 16 B (lane
+ * 16*kq + r: query 16*tile + r, dims [64*step + 16*kq, +16)); qmeta[256] float2 {qs, eq}: qs =
+ * max|q| / (127 |q|), eq >= | q/|q| - c qs |_2 rounded up, {0, -1} for padding queries, {0, 2} for
+ * a query without a usable norm */
+int spl_search_qprep8(const float *queries, int nq, void *qfrag8, void *qmeta, hipStream_t stream);
+/* spl_search_mma_pass on the int8 copy.  With approx = dot(codes) * rs[row] * qs[q] and B =
+ * err[row] + eq[q] * (1 + err[row]) + 4e-4 + 2e-6 (|approx - fp32 cosine of the exact kernel| <= B):
+ * mode 0: bmax = per-tile maximum of approx - B over the live rows with rs > 0, a lower bound of a
+ * real similarity, so the threshold takes delta2 = 0; mode 1: a live row is a candidate when
+ * approx + B >= thr[q] or err[row] >= 2; rows with err < 0 never are. */
+int spl_search_mma_pass8(spl_arena_t a, const void *qfrag8, const void *qmeta, int nq, long slot_begin,
+                         long slot_end, uint64_t mask, int mode, const float *thr, float *bmax, uint32_t *cnt,
+                         uint32_t *cand, int capb, int grid, hipStream_t stream);
 /* slot cores (128 B each) of n result entries (spl_search result layout) -> out_cores[n][128] */
 int spl_search_cores(spl_arena_t a, const void *result, int n, void *out_cores, hipStream_t stream);
 /* over[q] = 1 when cnt[q][0..nblk) has a segment count > capb (the query must be redone exactly) */

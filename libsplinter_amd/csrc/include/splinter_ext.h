@@ -116,6 +116,9 @@ typedef struct spl_probe_stats {
   uint64_t rebuilds, reclaimed, moved, pad;
 } spl_probe_stats;
 int   spl_hbm_probe_stats(spl_store *s, spl_probe_stats *out);
+/* Vector copies an hbm: store's arena carries beside the fp32 rows (bit 0: bf16, bit 1: the opt-in
+ * int8 copy of SPLINTER_HBM_VEC8=1); a node: store: those every shard carries.  < 0: no HBM store. */
+int   spl_hbm_vector_copies(spl_store *s);
 /* Tombstone maintenance: every live key moves into the first tombstone on its own probe path and
  * the tombstones left at the end of each cluster become never-used slots again, so misses stop at
  * the cluster's new end.  ONLINE: safe beside batch and per-call ops of every process -- each move

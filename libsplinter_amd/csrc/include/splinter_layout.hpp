@@ -42,6 +42,17 @@ constexpr size_t kOffHash = 0, kOffEpoch = 8, kOffValOff = 16, kOffValLen = 20,
 //                         operand the batched search's candidate pass streams (half the bytes of
 //                         the fp32 rows, contiguous); written under the slot's seqlock with the
 //                         fp32 vector by every embedding writer
+//   q8meta [slots] float2 SPL_ARENA_VEC8 arenas only, at the next 4-KiB boundary after the data
+//                         above (nrm2 and vec16 exist only with SPL_ARENA_VEC16; the two copies are
+//                         independent): {rs, err} of each slot's int8 row.  With n2 the squared norm
+//                         of the vector v, m its largest magnitude and codes c_d = rint(v_d 127 / m):
+//                           no vector (cleared, never set, n2 == 0)   {0, -1}  never a candidate
+//                           0 < n2 <= 2e-12, or n2 / m not finite     {0, 2}   always a candidate of
+//                                                                     the emit pass (the re-score decides)
+//                           otherwise   rs = m / (127 |v|),  err >= | v/|v| - c rs |_2 (rounded up)
+//   vec8 [slots][768]     SPL_ARENA_VEC8 arenas only, at the next 4-KiB boundary: the codes c (int8,
+//                         768 contiguous bytes per slot), the operand of the int8 candidate pass;
+//                         written with q8meta under the slot's seqlock by every embedding writer
 constexpr size_t kSideAlign = 4096;
 constexpr size_t kSideHdrBytes = 4096;
 constexpr size_t kVec16Bytes = kEmbedDim * 2;
@@ -52,8 +63,18 @@ SPL_HD size_t side_offset(size_t slots, size_t stride, size_t max_val) {
 }
 SPL_HD size_t side_nrm2_offset() { return kSideHdrBytes; }
 SPL_HD size_t side_vec16_offset(size_t slots) { return kSideHdrBytes + side_align_up(slots * 4); }
-SPL_HD size_t side_bytes(size_t slots, bool vec16) {
-  return vec16 ? side_vec16_offset(slots) + slots * kVec16Bytes : kSideHdrBytes;
+constexpr size_t kVec8Bytes = kEmbedDim;
+// (flag values of arena_api.h: SPL_ARENA_VEC16 = 4, SPL_ARENA_VEC8 = 8)
+constexpr uint32_t kSideVec16 = 4u, kSideVec8 = 8u;
+SPL_HD size_t side_q8meta_offset(size_t slots, uint32_t flags) {
+  return side_align_up((flags & kSideVec16) ? side_vec16_offset(slots) + slots * kVec16Bytes : kSideHdrBytes);
+}
+SPL_HD size_t side_vec8_offset(size_t slots, uint32_t flags) {
+  return side_q8meta_offset(slots, flags) + side_align_up(slots * 8);
+}
+SPL_HD size_t side_bytes(size_t slots, uint32_t flags) {
+  if (flags & kSideVec8) return side_vec8_offset(slots, flags) + slots * kVec8Bytes;
+  return (flags & kSideVec16) ? side_vec16_offset(slots) + slots * kVec16Bytes : kSideHdrBytes;
 }
 
 // probe-chain statistics (ArenaSide, and spl_hbm_probe_stats): a pass over the slot array

@@ -347,7 +347,7 @@ class HbmArena:
     def embedding_matrix(self) -> torch.Tensor:
         """[slots, 768] fp32 strided view of every slot's vector (zero copy).  Writes through this view
         bypass the embedding writers: call :meth:`rebuild_vec16` afterwards so the side region's bf16
-        copy (what the batched search streams) matches."""
+        and int8 copies (what the batched search streams) match."""
         assert self.embeddings
         base = self.desc.base + 5440 + 128
         flat = _device_view(base, self.slots * 3200 - 128, dtype=torch.float32)
@@ -371,10 +371,32 @@ class HbmArena:
     def has_vec16(self) -> bool:
         return bool(self.desc.flags & 4)
 
+    @property
+    def has_vec8(self) -> bool:
+        """The arena carries the opt-in int8 vector copy (created under SPLINTER_HBM_VEC8=1)."""
+        return bool(self.desc.flags & 8)
+
     def rebuild_vec16(self) -> None:
-        """Recompute the bf16 vector copy and squared norms from the fp32 vectors (spl_arena_vec16_rebuild)."""
+        """Recompute the bf16 vector copy and squared norms from the fp32 vectors
+        (spl_arena_vec16_rebuild), and the int8 copy where the arena has one (spl_arena_vec8_rebuild)."""
         if self.has_vec16:
             _check(self._H.spl_arena_vec16_rebuild(self.desc, _stream()), "arena_vec16_rebuild")
+        if self.has_vec8:
+            _check(self._H.spl_arena_vec8_rebuild(self.desc, _stream()), "arena_vec8_rebuild")
+
+    def vec8_view(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(meta [slots, 2] fp32 {rs, err}, vec8 [slots, 768] int8): the side region's int8 vector copy
+        and its per-row scale and error bound (zero copy; states: csrc/include/splinter_layout.hpp)."""
+        if not self.has_vec8:
+            raise ValueError("arena has no int8 vector copy")
+        al = lambda v: (v + self.SIDE_ALIGN - 1) // self.SIDE_ALIGN * self.SIDE_ALIGN  # noqa: E731
+        off = self.SIDE_HDR
+        if self.has_vec16:
+            off = al(self.SIDE_HDR + al(self.slots * 4) + self.slots * 768 * 2)
+        sb = self._side_base()
+        meta = _device_view(sb + off, self.slots * 8, dtype=torch.float32).view(self.slots, 2)
+        v8 = _device_view(sb + off + al(self.slots * 8), self.slots * 768).view(torch.int8)
+        return meta, v8.view(self.slots, 768)
 
     def vec16_view(self) -> Tuple[torch.Tensor, torch.Tensor]:
         """(nrm2 [slots] fp32, vec16 [slots, 768] bf16): the side region's squared norms and bf16

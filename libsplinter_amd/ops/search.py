@@ -22,6 +22,10 @@ MMA_GRID = 256       # persistent blocks of the MFMA pass (one per CU); candidat
 # |cos_bf16 - cos| <= 2u + u^2 (u = 2^-8: both operands rounded once to bf16,
 # Cauchy-Schwarz over the 768 products) plus fp32 accumulation / norm error
 DELTA = 2.0 ** -7 + 2.0 ** -16 + 4e-4
+# the int8 candidate pass carries its own per-row bound; of DELTA it keeps only the last term,
+# the real cosine against the exact kernel's fp32 cosine (the similarity floor's allowance)
+DELTA8 = 4e-4
+COPY_KINDS = ("fp32", "bf16", "int8")  # spl_search_copy_kind
 
 
 def _lib():
@@ -39,6 +43,13 @@ def _lib():
         L.spl_search_rescore.argtypes = [N.Arena, P, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float,
                                          ctypes.c_uint64, P, P, ctypes.c_int, ctypes.c_int, P, P]
         L.spl_search_rescore.restype = ctypes.c_int
+        L.spl_search_copy_kind.argtypes = [N.Arena]
+        L.spl_search_copy_kind.restype = ctypes.c_int
+        L.spl_search_qprep8.argtypes = [P, ctypes.c_int, P, P, P]
+        L.spl_search_qprep8.restype = ctypes.c_int
+        L.spl_search_mma_pass8.argtypes = [N.Arena, P, P, ctypes.c_int, ctypes.c_long, ctypes.c_long,
+                                           ctypes.c_uint64, ctypes.c_int, P, P, P, P, ctypes.c_int, ctypes.c_int, P]
+        L.spl_search_mma_pass8.restype = ctypes.c_int
         L._search_declared = True
     return L
 
@@ -80,8 +91,8 @@ class VectorSearch:
         return torch.cat(outs_i), torch.cat(outs_s), torch.cat(outs_d)
 
     def search_batch(self, queries: torch.Tensor, k: int = 10, min_sim: float = -2.0, max_dist: float = 3.4e38,
-                     label_mask: int = 0, capb: int = 64, sample: Optional[int] = None, stats: Optional[dict] = None
-                     ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+                     label_mask: int = 0, capb: int = 64, sample: Optional[int] = None, stats: Optional[dict] = None,
+                     copy: str = "auto") -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """Many-query search on the matrix cores; same results as `search` (exact fp32 ranking).
 
         Per launch of up to 512 queries: a bf16 MFMA pass over a slot sample gives a per-query
@@ -89,6 +100,13 @@ class VectorSearch:
         candidates above it, and a fp32 re-score with the exact kernel's arithmetic ranks them.
         Each of the MMA_GRID blocks keeps up to `capb` candidates per query; a query whose
         segment overflows anywhere is redone with the exact kernel.
+
+        ``copy``: "auto" streams the arena's int8 copy where it has one (SPLINTER_HBM_VEC8=1 at
+        creation; SPLINTER_SEARCH_VEC8=0 ignores it), else the bf16 copy / the fp32 rows; "int8"
+        demands the int8 copy; "bf16" takes the bf16 pass (on the bf16 copy, or the fp32 rows of
+        an arena without one).  The int8 pass bounds every row's error itself:
+        its sampled tile maxima are lower bounds of real similarities, so the threshold is the
+        k-th largest as it stands.  ``stats["copy"]`` names the operand used.
         """
         q = queries.to(device="cuda", dtype=torch.float32).reshape(-1, 768).contiguous()
         slots = self.arena.slots
@@ -96,6 +114,15 @@ class VectorSearch:
             raise ValueError(f"k must be 1..{MAX_K}")
         if q.shape[0] < 32 or slots < TILE:
             return self.search(q, k, min_sim, max_dist, label_mask)
+        if copy not in ("auto", "int8", "bf16"):
+            raise ValueError("copy must be 'auto', 'int8' or 'bf16'")
+        kind = COPY_KINDS[self.L.spl_search_copy_kind(self.arena.desc)]
+        if copy == "int8" and not self.arena.has_vec8:
+            raise ValueError("arena has no int8 vector copy")
+        i8 = copy == "int8" or (copy == "auto" and kind == "int8")
+        if not i8 and kind == "int8":  # what spl_search_mma_pass streams
+            kind = "bf16" if self.arena.has_vec16 else "fp32"
+        delta = DELTA8 if i8 else DELTA
         st = torch.cuda.current_stream().cuda_stream
         if sample is None:
             sample = min(slots, max(TILE * 4096, slots // 16))
@@ -107,28 +134,38 @@ class VectorSearch:
             qq = q[b: b + MMA_Q]
             n = qq.shape[0]
             qpad = MMA_Q
-            qb = torch.zeros(qpad, 768, dtype=torch.bfloat16, device="cuda")
-            qb[:n] = (qq / qq.norm(dim=1, keepdim=True).clamp_min(1e-30)).to(torch.bfloat16)
-            # fragment order [q/16][24 steps][4 kq][16 r][8]: lane 16*kq + r of a wave load
-            qf = qb.view(qpad // 16, 16, 24, 4, 8).permute(0, 2, 3, 1, 4).contiguous()
-            floor = torch.full((n,), float(min_sim) - DELTA, device="cuda")
+            if i8:
+                qf, qmeta = self.qprep8(qq)
+            else:
+                qb = torch.zeros(qpad, 768, dtype=torch.bfloat16, device="cuda")
+                qb[:n] = (qq / qq.norm(dim=1, keepdim=True).clamp_min(1e-30)).to(torch.bfloat16)
+                # fragment order [q/16][24 steps][4 kq][16 r][8]: lane 16*kq + r of a wave load
+                qf = qb.view(qpad // 16, 16, 24, 4, 8).permute(0, 2, 3, 1, 4).contiguous()
+
+            def mma_pass(end, mode, thr_p, bmax_p, cnt_p, cand_p, cb):
+                if i8:
+                    return self.L.spl_search_mma_pass8(self.arena.desc, qf.data_ptr(), qmeta.data_ptr(), n, 0, end,
+                                                       label_mask, mode, thr_p, bmax_p, cnt_p, cand_p, cb, MMA_GRID, st)
+                return self.L.spl_search_mma_pass(self.arena.desc, qf.data_ptr(), n, 0, end, label_mask, mode,
+                                                  thr_p, bmax_p, cnt_p, cand_p, cb, MMA_GRID, st)
+
+            floor = torch.full((n,), float(min_sim) - delta, device="cuda")
             if bounded:
                 thr = floor
             else:
                 bmax = torch.empty(sample // TILE, n, dtype=torch.float32, device="cuda")
-                rc = self.L.spl_search_mma_pass(self.arena.desc, qf.data_ptr(), n, 0, sample, label_mask, 0, None,
-                                                bmax.data_ptr(), None, None, 0, MMA_GRID, st)
+                rc = mma_pass(sample, 0, None, bmax.data_ptr(), None, None, 0)
                 if rc != 0:
                     raise RuntimeError(f"spl_search_mma_pass(bmax) failed ({rc})")
                 kk = min(k, bmax.shape[0])
                 kth = bmax.topk(kk, dim=0).values[-1]
                 if kk < k:
                     kth = torch.full_like(kth, -3.0e38)
-                thr = torch.maximum(kth - 2 * DELTA, floor)
+                # (int8: every sampled maximum is a lower bound of a real similarity already)
+                thr = torch.maximum(kth if i8 else kth - 2 * DELTA, floor)
             cnt = torch.zeros(n, MMA_GRID, dtype=torch.int32, device="cuda")
             cand = torch.empty(n * MMA_GRID * capb, dtype=torch.int32, device="cuda")
-            rc = self.L.spl_search_mma_pass(self.arena.desc, qf.data_ptr(), n, 0, slots, label_mask, 1,
-                                            thr.data_ptr(), None, cnt.data_ptr(), cand.data_ptr(), capb, MMA_GRID, st)
+            rc = mma_pass(slots, 1, thr.data_ptr(), None, cnt.data_ptr(), cand.data_ptr(), capb)
             if rc != 0:
                 raise RuntimeError(f"spl_search_mma_pass(cand) failed ({rc})")
             res = torch.empty(n * k * 4, dtype=torch.int32, device="cuda")
@@ -153,8 +190,35 @@ class VectorSearch:
             outs_s.append(sim)
             outs_d.append(dist)
         if stats is not None:
-            stats.update(overflow=nover, candidates=ncand, sample=sample)
+            stats.update(overflow=nover, candidates=ncand, sample=sample, copy="int8" if i8 else kind)
         return torch.cat(outs_i), torch.cat(outs_s), torch.cat(outs_d)
+
+    def qprep8(self, queries: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """queries [n <= 256, 768] fp32 -> (codes int8 [16, 12, 4, 16, 16] in the int8 pass's fragment
+        order, qmeta [256, 2] fp32 {qs, eq}) as spl_search_qprep8 writes them."""
+        q = queries.to(device="cuda", dtype=torch.float32).reshape(-1, 768).contiguous()
+        if not 1 <= q.shape[0] <= MMA_Q:
+            raise ValueError(f"1..{MMA_Q} queries per block")
+        qf = torch.empty(MMA_Q // 16, 12, 4, 16, 16, dtype=torch.int8, device="cuda")
+        qmeta = torch.empty(MMA_Q, 2, dtype=torch.float32, device="cuda")
+        rc = self.L.spl_search_qprep8(q.data_ptr(), q.shape[0], qf.data_ptr(), qmeta.data_ptr(),
+                                      torch.cuda.current_stream().cuda_stream)
+        if rc != 0:
+            raise RuntimeError(f"spl_search_qprep8 failed ({rc})")
+        return qf, qmeta
+
+    def bmax_pass8(self, qf: torch.Tensor, qmeta: torch.Tensor, nq: int, slot_end: int,
+                   label_mask: int = 0) -> torch.Tensor:
+        """The int8 threshold-sample pass over slots [0, slot_end): [tiles, nq] per-tile maxima of
+        approx - B (-FLT_MAX for a tile without a live row that carries codes)."""
+        tiles = (slot_end + TILE - 1) // TILE
+        bmax = torch.empty(tiles, nq, dtype=torch.float32, device="cuda")
+        rc = self.L.spl_search_mma_pass8(self.arena.desc, qf.data_ptr(), qmeta.data_ptr(), nq, 0, slot_end,
+                                         label_mask, 0, None, bmax.data_ptr(), None, None, 0, MMA_GRID,
+                                         torch.cuda.current_stream().cuda_stream)
+        if rc != 0:
+            raise RuntimeError(f"spl_search_mma_pass8(bmax) failed ({rc})")
+        return bmax
 
     def keys_of(self, idx: torch.Tensor) -> List[List[Optional[str]]]:
         """Map slot indices to key strings (one gather of the slot cores)."""

@@ -2,7 +2,12 @@
 batched MFMA search against the exact fp32 kernel on an arena of N embedded slots.
 
 python scripts/search_bench.py [--slots 25000000] [--nq 512] [--k 10] [--iters 3]
-Synthetic clustered 768-d vectors (random, not a real corpus); prints one JSON line.
+                               [--data clustered|iid] [--copy auto|bf16|int8|both]
+Synthetic 768-d vectors (random, not a real corpus): clustered (4096 centres, sigma 0.5) or i.i.d.
+normal.  Prints one JSON line per arm: `--copy both` on an arena created under SPLINTER_HBM_VEC8=1
+times the bf16 and the int8 candidate copy on the same vectors in one process; per arm the QPS,
+the time of one candidate pass alone, the candidates per query, the overflow count and recall@k /
+identity of the top-k against the exact kernel.
 200M x 768 across 8 GPUs = 25M slots per GPU (80 GB of 3200-B slots in HBM).
 """
 import argparse
@@ -14,6 +19,53 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
+def _pass_ms(vs, ar, q, copy, iters):
+    """One candidate (emit) pass over the whole arena for the first 256 queries, alone: thresholds
+    from the arm's own sample pass, best of `iters` by device events."""
+    import torch
+    from libsplinter_amd.ops.search import MMA_GRID, MMA_Q, TILE
+    qq = q[:MMA_Q].contiguous()
+    n, slots = qq.shape[0], ar.slots
+    st = torch.cuda.current_stream().cuda_stream
+    sample = max(TILE, min(slots, max(TILE * 4096, slots // 16)) // TILE * TILE)
+    bmax = torch.empty(sample // TILE, n, dtype=torch.float32, device="cuda")
+    cnt = torch.zeros(n, MMA_GRID, dtype=torch.int32, device="cuda")
+    cand = torch.empty(n * MMA_GRID * 64, dtype=torch.int32, device="cuda")
+    if copy == "int8":
+        qf, qmeta = vs.qprep8(qq)
+
+        def run(end, mode, thr):
+            return vs.L.spl_search_mma_pass8(ar.desc, qf.data_ptr(), qmeta.data_ptr(), n, 0, end, 0, mode,
+                                             thr.data_ptr() if thr is not None else None,
+                                             bmax.data_ptr() if mode == 0 else None, cnt.data_ptr(), cand.data_ptr(),
+                                             64, MMA_GRID, st)
+        margin = 0.0
+    else:
+        from libsplinter_amd.ops.search import DELTA
+        qb = torch.zeros(MMA_Q, 768, dtype=torch.bfloat16, device="cuda")
+        qb[:n] = (qq / qq.norm(dim=1, keepdim=True).clamp_min(1e-30)).to(torch.bfloat16)
+        qf = qb.view(MMA_Q // 16, 16, 24, 4, 8).permute(0, 2, 3, 1, 4).contiguous()
+
+        def run(end, mode, thr):
+            return vs.L.spl_search_mma_pass(ar.desc, qf.data_ptr(), n, 0, end, 0, mode,
+                                            thr.data_ptr() if thr is not None else None,
+                                            bmax.data_ptr() if mode == 0 else None, cnt.data_ptr(), cand.data_ptr(),
+                                            64, MMA_GRID, st)
+        margin = 2 * DELTA
+    assert run(sample, 0, None) == 0
+    thr = (bmax.topk(10, dim=0).values[-1] - margin).contiguous()
+    best = 1e9
+    for _ in range(iters + 1):
+        cnt.zero_()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        assert run(slots, 1, thr) == 0
+        e1.record()
+        torch.cuda.synchronize()
+        best = min(best, e0.elapsed_time(e1))
+    return best
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--slots", type=int, default=25_000_000)
@@ -22,6 +74,11 @@ def main():
     ap.add_argument("--iters", type=int, default=3)
     ap.add_argument("--recall-queries", type=int, default=32)
     ap.add_argument("--exact", action="store_true", help="also time the exact fp32 kernel on all queries")
+    ap.add_argument("--data", default="clustered", choices=["clustered", "iid"])
+    ap.add_argument("--copy", default="auto", choices=["auto", "bf16", "int8", "both"],
+                    help="candidate copy per arm (int8 / both need an arena created under SPLINTER_HBM_VEC8=1)")
+    ap.add_argument("--capb", type=int, default=64,
+                    help="candidates kept per (block, query) segment; the product path (spl_search_batch) uses 64")
     a = ap.parse_args()
     import torch
     from libsplinter_amd.ops.arena import HbmArena, format_keys, format_values
@@ -33,6 +90,13 @@ def main():
         t0 = time.time()
         g = torch.Generator(device="cuda").manual_seed(0)
         centers = torch.randn(4096, 768, device="cuda", generator=g)
+
+        def draw(m):
+            if a.data == "iid":
+                return torch.randn(m, 768, device="cuda", generator=g)
+            lab = torch.randint(0, 4096, (m,), device="cuda", generator=g)
+            return centers[lab] + 0.5 * torch.randn(m, 768, device="cuda", generator=g)
+
         em = ar.embedding_matrix()
         step = 2_000_000
         for b in range(0, n, step):
@@ -45,40 +109,48 @@ def main():
         # vectors straight into the slot embedding fields (occupied or not: the kernels skip free slots)
         for b in range(0, a.slots, step):
             m = min(step, a.slots - b)
-            lab = torch.randint(0, 4096, (m,), device="cuda", generator=g)
-            em[b: b + m] = centers[lab] + 0.5 * torch.randn(m, 768, device="cuda", generator=g)
-        ar.rebuild_vec16()  # raw writes through the view: the bf16 copy the search streams, recomputed
+            em[b: b + m] = draw(m)
+        ar.rebuild_vec16()  # raw writes through the view: the copies the search streams, recomputed
         torch.cuda.synchronize()
         fill_s = time.time() - t0
         vs = VectorSearch(ar, grid=1024)
-        lab = torch.randint(0, 4096, (a.nq,), device="cuda", generator=g)
-        q = centers[lab] + 0.5 * torch.randn(a.nq, 768, device="cuda", generator=g)
-        st = {}
-        vs.search_batch(q, k=a.k, stats=st)  # warmup
-        torch.cuda.synchronize()
-        ts = []
-        for _ in range(a.iters):
-            t = time.perf_counter()
-            idx, sim, _ = vs.search_batch(q, k=a.k, stats=st)
-            torch.cuda.synchronize()
-            ts.append(time.perf_counter() - t)
-        best = min(ts)
+        q = draw(a.nq)
         rq = min(a.recall_queries, a.nq)
         t = time.perf_counter()
         ei, es, _ = vs.search(q[:rq], k=a.k)
         torch.cuda.synchronize()
         exact_s = time.perf_counter() - t
-        hit = 0
-        for j in range(rq):
-            hit += len(set(idx[j].tolist()) & set(ei[j].tolist()))
-        out = {"bench": "vector_search", "slots": a.slots, "embedded": a.slots, "occupied": n, "nq": a.nq,
-               "k": a.k, "qps": a.nq / best, "ms_per_batch": best * 1e3, "recall_at_k": hit / (rq * a.k),
-               "exact_match": bool(torch.equal(idx[:rq], ei)), "candidates_per_query": st["candidates"] / a.nq,
-               "overflow_queries": st["overflow"], "exact_kernel_qps": rq / exact_s,
-               "scan_GBps": a.slots * (1536 if ar.has_vec16 else 3200) / best / 1e9 * ((a.nq + 255) // 256),
-               "candidate_rows": "bf16 copy (side region)" if ar.has_vec16 else "fp32 slot rows", "fill_s": round(fill_s, 1),
-               "data": "synthetic clustered (4096 centres, sigma 0.5), fp32 768-d in slots"}
-        print(json.dumps(out), flush=True)
+        arms = ["bf16", "int8"] if a.copy == "both" else [a.copy]
+        for copy in arms:
+            st = {}
+            vs.search_batch(q, k=a.k, stats=st, copy=copy, capb=a.capb)  # warmup
+            torch.cuda.synchronize()
+            ts = []
+            for _ in range(a.iters):
+                t = time.perf_counter()
+                idx, sim, _ = vs.search_batch(q, k=a.k, stats=st, copy=copy, capb=a.capb)
+                torch.cuda.synchronize()
+                ts.append(time.perf_counter() - t)
+            best = min(ts)
+            hit = 0
+            for j in range(rq):
+                hit += len(set(idx[j].tolist()) & set(ei[j].tolist()))
+            used = st["copy"]
+            row_bytes = {"int8": 768, "bf16": 1536, "fp32": 3200}[used]
+            out = {"bench": "vector_search", "arm": used, "slots": a.slots, "embedded": a.slots, "occupied": n,
+                   "nq": a.nq, "k": a.k, "capb": a.capb, "qps": a.nq / best, "ms_per_batch": best * 1e3,
+                   "ms_per_candidate_pass": _pass_ms(vs, ar, q, used, a.iters),
+                   "recall_at_k": hit / (rq * a.k), "exact_match": bool(torch.equal(idx[:rq], ei)),
+                   "sims_identical": bool(torch.equal(sim[:rq], es)),
+                   "candidates_per_query": st["candidates"] / a.nq, "overflow_queries": st["overflow"],
+                   "exact_kernel_qps": rq / exact_s,
+                   "scan_GBps": a.slots * row_bytes / best / 1e9 * ((a.nq + 255) // 256),
+                   "candidate_rows": {"int8": "int8 copy (side region)", "bf16": "bf16 copy (side region)",
+                                      "fp32": "fp32 slot rows"}[used],
+                   "fill_s": round(fill_s, 1),
+                   "data": ("synthetic clustered (4096 centres, sigma 0.5)" if a.data == "clustered"
+                            else "synthetic i.i.d. normal") + ", fp32 768-d in slots"}
+            print(json.dumps(out), flush=True)
     finally:
         ar.close()
 
