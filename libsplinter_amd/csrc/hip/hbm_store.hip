@@ -1118,7 +1118,7 @@ long HbmStore::search_all(const float* q, uint64_t mask, float min_sim, float ma
 // MFMA passes of search_kernels.hip): per block of 256 queries a bf16 pass over a slot sample gives a
 // per-query candidate threshold (k-th largest per-tile maximum - 2 delta), a bf16 pass over the
 // whole arena (the side region's bf16 copy where the arena has one) emits the candidates above it
-// (an arena with the opt-in int8 copy: both passes on it, search_kernels.hip mf8, with a per-row bound),
+// (an arena with the opt-in int8 copy: both passes on it, search_kernels.hip side::OpInt8, with a per-row bound),
 // and an fp32 re-score with the exact kernel's arithmetic ranks them; a query whose candidate
 // segment overflowed anywhere is redone with the exact kernel.  Results: out[q * k + j], ranked by
 // similarity desc, distance asc (reference splinter_cli_cmd_search.c:374-416); unused entries have

@@ -221,7 +221,7 @@ constexpr int kSteps = kD / 32;           // 24 K-chunks of 32 dims per tile
 constexpr int kChunk = kTile * 128;       // 32 KB of fp32 per chunk
 constexpr int kRing = 4;                  // LDS ring depth (chunks)
 constexpr int kAhead = kRing - 1;         // DMA lead (chunks)
-constexpr int kDist = 3;                  // query-fragment lead (chunks), = kAhead: see SPL_STEP_SYNC
+constexpr int kDist = 3;                  // query-fragment lead (chunks), = kAhead: see step_sync
 constexpr int kDma = kChunk / 1024 / 4;   // DMA wave-instructions per wave per chunk (8)
 constexpr int kRsrcWord3 = 0x00020000;    // gfx9 raw buffer
 static_assert(kThreads == kQ, "one LDS candidate counter per thread");
@@ -263,12 +263,28 @@ __device__ __forceinline__ bf16x8 load_qfrag(rsrc_t r, int voff, int qtile, int 
 // one of them was a step 0; the first tile's prologue (fragments 0..2, then
 // DMA 0..2) gives lower bounds 16 at s = 0 and 22 at s = 1.  Wait + barrier
 // carry a memory clobber: no LDS read moves above them, no DMA below.
-#define SPL_STEP_SYNC(N) asm volatile("s_waitcnt vmcnt(" #N ")\n\ts_barrier" ::: "memory")
+template <int N>
+__device__ __forceinline__ void step_sync() {
+  asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(N) : "memory");
+}
 __device__ __forceinline__ void wait_vm0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 __device__ __forceinline__ void raw_barrier() {
   asm volatile("" ::: "memory");
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
+}
+// this wave's LDS stores have landed and every wave is here (a raw s_barrier does not wait for them)
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+// candidate `slot` of query q into the block-private segment cand[q][block][capb]: the position
+// comes from an LDS counter, the global write needs no return value
+__device__ __forceinline__ void emit_cand(uint32_t* ncand, uint32_t* cand, int q, int capb, uint32_t slot) {
+  const uint32_t p = atomicAdd(&ncand[q], 1u);
+  if (p < (uint32_t)capb) cand[((long)q * gridDim.x + blockIdx.x) * capb + p] = slot;
+}
+// max over the four lanes (fq = 0..3) that hold one query's rows
+__device__ __forceinline__ float quad_max(float v) {
+  v = fmaxf(v, __shfl_xor(v, 16, 64));
+  return fmaxf(v, __shfl_xor(v, 32, 64));
 }
 
 template <int MODE>  // MODE 0 = per-tile max per query, 1 = emit candidates
@@ -351,13 +367,13 @@ __global__ __launch_bounds__(kThreads, 1) void k_search_mma(spl_arena_t aa, cons
       // chunk s landed (this wave's DMA) and, after the barrier, every wave's
       // DMA landed and every wave is done with chunk s-1's ring buffer
       if (s == 0)
-        SPL_STEP_SYNC(16);
+        step_sync<16>();
       else if (s == 1)
-        SPL_STEP_SYNC(22);
+        step_sync<22>();
       else if (s == 2)
-        SPL_STEP_SYNC(26);
+        step_sync<26>();
       else
-        SPL_STEP_SYNC(24);
+        step_sync<24>();
       // query fragments are periodic in the step: the ring runs across tiles
 #pragma unroll
       for (int j = 0; j < kNJ; ++j)
@@ -412,9 +428,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_search_mma(spl_arena_t aa, cons
       sm.live[row] = h != 0 && (!mask || (bl & mask) == mask) && sel > kMinNorm2 && start + row >= t * kTile;
       sm.inv[row] = sel > 0.f ? rsqrtf(sel) : 0.f;
     }
-    // the live / inv stores must have landed before another wave reads them: a raw s_barrier does
-    // not wait for this wave's LDS stores
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    lds_barrier();  // the live / inv stores, before another wave reads them
     {
       const f32x4* invp = (const f32x4*)(sm.inv + fq * 4);  // rows 16i + 4fq + r, r = 0..3
       const int4* livp = (const int4*)(sm.live + fq * 4);
@@ -434,11 +448,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_search_mma(spl_arena_t aa, cons
             if (MODE == 0) {
               if (lvr[r]) best[j] = fmaxf(best[j], sim);
             } else if (sim >= thr[j] && lvr[r]) {
-              // block-private segment [q][block][capb]: the slot index comes
-              // from an LDS counter, the global write needs no return value
-              const int q = (qtile0 + j) * 16 + fr;
-              const uint32_t p = atomicAdd(&sm.ncand[q], 1u);
-              if (p < (uint32_t)capb) cand[((long)q * gridDim.x + blockIdx.x) * capb + p] = (uint32_t)(start + i * 16 + fq * 4 + r);
+              emit_cand(sm.ncand, cand, (qtile0 + j) * 16 + fr, capb, (uint32_t)(start + i * 16 + fq * 4 + r));
             }
           }
       }
@@ -446,8 +456,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_search_mma(spl_arena_t aa, cons
 #pragma unroll
         for (int j = 0; j < kNJ; ++j) {
           const int q = (qtile0 + j) * 16 + fr;
-          float bj = fmaxf(best[j], __shfl_xor(best[j], 16, 64));
-          bj = fmaxf(bj, __shfl_xor(bj, 32, 64));
+          const float bj = quad_max(best[j]);
           if (fq == 0 && q < nq) bmax[(t - tile_base) * nq + q] = bj;
         }
       }
@@ -464,229 +473,110 @@ __global__ __launch_bounds__(kThreads, 1) void k_search_mma(spl_arena_t aa, cons
 }  // namespace mf
 
 // ---------------------------------------------------------------------------
-// The same pass on the side region's bf16 copy (SPL_ARENA_VEC16 arenas, splinter_layout.hpp): every
-// slot's vector as 1536 contiguous bytes (half the fp32 row, no 3200-B stride) and its squared norm
-// precomputed by the writer.  The operands are the values the fp32 pass converts in registers
-// (v_cvt_pk_bf16_f32 = round to nearest even, as the writers store them) and the norm is the fp32
-// one, so the candidate bound and the result are the fp32 pass's.  K-chunks of 32 dims = 64 B per row:
-// a 16 KB chunk per 256-row tile, 4 LDS-DMA wave-instructions per wave, the A fragments read straight
-// as bf16 (one ds_read_b128 each).  Rows are 64 B, so a ds_read_b128 lane group (16 lanes) would hit
-// the same 4 banks for rows r and r + 4: the 16-B unit u of row r is stored at u ^ f((r >> 2) & 3)
-// with f = {0, 2, 3, 1}, which gives every gfx950 b128 lane group 16 distinct 4-bank groups (checked
-// by hand over the four groups); the XOR goes on the global source address (glds writes lane-linearly).
-namespace mf16 {
+// The same pass on the side region's vector copies (splinter_layout.hpp): every slot's vector as
+// contiguous bytes (no 3200-B stride), with what the epilogue needs per row precomputed by the
+// writer.  One streaming kernel, k_search_side<Op, MODE>; the operand policies below carry what
+// differs between the copies and nothing else:
+//   OpBf16 (SPL_ARENA_VEC16): 1536-B rows and the fp32 squared norm.  The operands are the values
+//     the fp32 pass converts in registers (v_cvt_pk_bf16_f32 = round to nearest even, as the writers
+//     store them) and the norm is the fp32 one, so the candidate bound and the result are the fp32
+//     pass's.  24 K-chunks of 32 dims on v_mfma_f32_16x16x32_bf16.
+//   OpInt8 (SPL_ARENA_VEC8): 768-B rows and {rs, err} per row, 12 K-chunks of 64 dims on
+//     v_mfma_i32_16x16x64_i8; its arithmetic and bound are described at the policy.
+// Either way a K-chunk is 64 B per row: a 16 KB chunk per 256-row tile, the A fragments read
+// straight as one ds_read_b128 each.  Lane (fr, fq) holds bytes [16 fq, +16) of its row piece /
+// query piece as the A / B fragment: both operands put the same dims in the same lane group and
+// byte, so the sum over k pairs them whatever order the instruction walks k in.
+//
+// Two waves per SIMD: wave w owns the 64 queries of group w & 3 against slot half w >> 2 (8 x 4
+// accumulator tiles, 128 registers), so one wave's matrix work runs while its partner waits on the
+// DMA / barrier (with one wave per SIMD the two were serialised: without its MFMAs that pass took
+// 8.4 of its 13.5 ms, profiles/r5/search_probes).  The query fragments of a K-chunk (16 KB) arrive
+// by LDS-DMA beside the slot rows, so no wave stages them in registers three chunks ahead.
+namespace side {
 using mf::bf16x8;
 using mf::f32x4;
 using mf::rsrc_t;
 using mf::lds_void;
-constexpr int kTile = mf::kTile, kQ = mf::kQ, kNJ = mf::kNJ, kSteps = mf::kSteps;
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+constexpr int kTile = mf::kTile, kQ = mf::kQ, kNJ = mf::kNJ;
 constexpr int kWaves = 8, kThreads = kWaves * 64;  // two waves per SIMD
-constexpr int kChunk = kTile * 64;        // 16 KB of bf16 slot rows per K-chunk
-constexpr int kQChunk = kQ * 64;          // 16 KB of bf16 query fragments per K-chunk
+constexpr int kChunk = kTile * 64;        // 16 KB of slot rows per K-chunk
+constexpr int kQChunk = kQ * 64;          // 16 KB of query fragments per K-chunk
 constexpr int kRing = mf::kRing, kAhead = mf::kAhead;
 constexpr int kRows = kTile / kWaves;     // slot rows a wave stages (DMA, metadata): 32
 constexpr int kBlk = 8;                   // 16-row blocks per wave: one slot half
+constexpr int kDmaPerStep = 2 + 2;        // LDS-DMA wave-instructions a wave issues per step: query + row pieces
 constexpr int kRsrcWord3 = mf::kRsrcWord3;
-struct Smem {
-  char ring[kRing][kChunk];   // 64 KB
-  char qring[kRing][kQChunk]; // 64 KB
-  __attribute__((aligned(16))) float inv[kTile];
-  __attribute__((aligned(16))) int live[kTile];
-  uint32_t ncand[kQ];
-  float pmax[kQ];             // MODE 0: the upper slot half's per-query maxima
-};
+
 // 16-B unit swizzle of the 64-B row pieces: physical unit = logical unit ^ rsw(row & 15).  gfx950
 // services a ds_read_b128 in the lane groups {0-3,12-15,20-27}, {4-11,16-19,28-31}, and the same
 // +32 (MI355X_MICROARCH.md, LDS); with the fragment read (lane -> row lane & 15, unit lane >> 4)
 // this one flip of unit bit 1 for rows 8-15 puts every group on 16 distinct 16-B bank slots (found
 // by exhaustive search).  The former {0,2,3,1}[(row >> 2) & 3], right for contiguous 16-lane
 // groups, cost 8 extra LDS cycles per read: a 56 % conflict rate (profiles/r5/search8/pmc_search.md).
+// The XOR goes on the global source address (the LDS-DMA writes lane-linearly).
 __device__ __forceinline__ int rsw(int r) { return ((r >> 3) & 1) << 1; }
 
-__device__ __forceinline__ rsrc_t tile_rsrc16(const spl::dev::Arena& a, long t, long slot_end) {
-  return __builtin_amdgcn_make_buffer_rsrc(a.vec16((size_t)mf::tile_start(t, slot_end)), 0, kTile * 1536, kRsrcWord3);
-}
-
-// Two waves per SIMD: wave w owns the 64 queries of group w & 3 against slot half w >> 2 (8 x 4
-// accumulator tiles, 128 registers), so one wave's matrix work runs while its partner waits on the
-// DMA / barrier (with one wave per SIMD the two were serialised: without its MFMAs that pass took
-// 8.4 of its 13.5 ms, profiles/r5/search_probes).  The query fragments of a K-chunk (16 KB) arrive
-// by LDS-DMA beside the slot rows, so no wave stages them in registers three chunks ahead.
-// In-order vmcnt: a wave issues per step (the metadata, 3 loads, at step 0, then) the DMA of chunk
-// s + 3, 2 query + 2 row pieces; younger than chunk s's DMA at the top of step s: 8, or 11 when one
-// of the two steps after its issue was a step 0 (s = 1, 2).
-template <int MODE>
-__global__ __launch_bounds__(kThreads, 1) void k_search_mma16(spl_arena_t aa, const void* __restrict__ qf, int nq,
-                                                             long slot_begin, long slot_end, uint64_t mask,
-                                                             const float* __restrict__ thr_in, float* __restrict__ bmax,
-                                                             uint32_t* __restrict__ cnt, uint32_t* __restrict__ cand,
-                                                             int capb) {
-  __shared__ __attribute__((aligned(16))) Smem sm;
-  const spl::dev::Arena a = spl::dev::from_api(aa);
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int fr = lane & 15, fq = lane >> 4;
-  const int qg = wave & 3, sh = wave >> 2;
-  const long tile_base = slot_begin / kTile;
-  const long tile_end = (slot_end + kTile - 1) / kTile, G = gridDim.x;
-  const long t0 = tile_base + blockIdx.x;
-  if (t0 >= tile_end) return;  // block-uniform
-  if (MODE == 1 && tid < kQ) sm.ncand[tid] = 0;
-
-  const rsrc_t qr = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(qf), 0, kQ * kD * 2, kRsrcWord3);
-  const int qtile0 = qg * kNJ;
-  // row DMA: wave-instruction k of a chunk fills rows 32w + 16k .. +16 (1 KB), lane l -> row +(l >> 2),
-  // physical unit l & 3 <- logical unit (l & 3) ^ rsw(row & 15); query DMA: instruction k brings the
-  // 1-KB fragment block of 16-query tile 2w + k for the chunk's step (lane-linear, as read)
-  int dvoff[2];
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const int row = wave * kRows + k * 16 + (lane >> 2);
-    dvoff[k] = row * 1536 + (((lane & 3) ^ rsw(row & 15)) << 4);
-  }
-  const float* nrm2 = a.nrm2();
-  // fragment read: row 16i + fr of this wave's slot half, logical unit fq
-  const int rdo = fr * 64 + ((fq ^ rsw(fr)) << 4) + sh * kBlk * 1024;
-
-  float thr[kNJ];
-#pragma unroll
-  for (int j = 0; j < kNJ; ++j) {
-    const int q = (qtile0 + j) * 16 + fr;
-    thr[j] = (MODE == 1 && q < nq) ? thr_in[q] : FLT_MAX;
-  }
-  auto issue = [&](rsrc_t er, int c, int slot) {
-#pragma unroll
-    for (int k = 0; k < 2; ++k)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(qr, (lds_void*)(sm.qring[slot] + (2 * wave + k) * 1024), 16, lane * 16,
-                                               ((2 * wave + k) * kSteps + c) * 1024, 0, 0);
-    char* dst = sm.ring[slot] + wave * kRows * 64;
-#pragma unroll
-    for (int k = 0; k < 2; ++k)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(er, (lds_void*)(dst + k * 1024), 16, dvoff[k], c * 64, 0, 0);
+// put_row's `cand` is what a row needs whatever the operand: a key, the label bits, and a slot of
+// this tile (the shifted last tile re-reads slots of the tile before it).
+struct OpBf16 {
+  typedef bf16x8 frag_t;
+  typedef f32x4 acc_t;
+  typedef float meta_t;                       // the row's squared norm
+  static constexpr int kSteps = kD / 32;      // K-chunks of 32 dims
+  static constexpr int kRowBytes = kD * 2;
+  static constexpr int kMetaLoads = 3;        // hash, bloom, nrm2[row]
+  static constexpr bool kCheckNq = false;     // queries >= nq carry a FLT_MAX threshold
+  struct __attribute__((aligned(16))) Lds {
+    float inv[kTile];
+    int live[kTile];
   };
-  const long last = tile_end - 1;
-  {
-    const rsrc_t er = tile_rsrc16(a, t0, slot_end);
-    for (int c = 0; c < kAhead; ++c) issue(er, c, c);
+  struct Q { float thr[kNJ]; };               // thresholds: registers across the K loop
+  struct Row { f32x4 iv; int lv[4]; };
+  static __device__ __forceinline__ const void* rows(const spl::dev::Arena& a, long slot) { return a.vec16((size_t)slot); }
+  static __device__ __forceinline__ meta_t no_meta() { return 0.f; }
+  static __device__ __forceinline__ meta_t load_meta(const spl::dev::Arena& a, long row) {
+    return __builtin_nontemporal_load(a.nrm2() + row);
   }
-
-  for (long t = t0; t < tile_end; t += G) {
-    const long start = mf::tile_start(t, slot_end);
-    const rsrc_t er_cur = tile_rsrc16(a, t, slot_end);
-    const rsrc_t er_next = tile_rsrc16(a, t + G < tile_end ? t + G : last, slot_end);
-    uint64_t h = 0, bl = 0;
-    float n2 = 0.f;
-    f32x4 acc[kBlk][kNJ];
-#pragma unroll
-    for (int i = 0; i < kBlk; ++i)
-#pragma unroll
-      for (int j = 0; j < kNJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-#pragma clang loop unroll(full)
-    for (int s = 0; s < kSteps; ++s) {
-      if (s == 1 || s == 2)
-        SPL_STEP_SYNC(11);
-      else
-        SPL_STEP_SYNC(8);
-      if (s == 0) {  // metadata of this wave's 32 rows (lanes 32-63 repeat 0-31)
-        const long row = start + wave * kRows + (lane & (kRows - 1));
-        const uint8_t* sp = a.slot((size_t)row);
-        h = __builtin_nontemporal_load((const uint64_t*)(sp + spl::kOffHash));
-        bl = __builtin_nontemporal_load((const uint64_t*)(sp + spl::kOffBloom));
-        n2 = __builtin_nontemporal_load(nrm2 + row);
-      }
-      const char* qs = sm.qring[s % kRing] + lane * 16;
-      bf16x8 bq[kNJ];
-#pragma unroll
-      for (int j = 0; j < kNJ; ++j) bq[j] = *(const bf16x8*)(qs + (qtile0 + j) * 1024);
-      const char* ch = sm.ring[s % kRing] + rdo;
-#pragma unroll
-      for (int i0 = 0; i0 < kBlk; i0 += 4) {
-        bf16x8 af[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) af[u] = *(const bf16x8*)(ch + (i0 + u) * 1024);
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-          for (int j = 0; j < kNJ; ++j)
-            acc[i0 + u][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[u], bq[j], acc[i0 + u][j], 0, 0, 0);
-        // the next chunk's DMA after the first MFMA group: its issue overlaps matrix work (11.92 vs
-        // 12.15 ms per pass issued before the group; s_setprio around the groups: neutral)
-        if (i0 == 0) issue(s + kAhead < kSteps ? er_cur : er_next, (s + kAhead) % kSteps, (s + kAhead) % kRing);
-      }
-    }
-    {
-      constexpr float kMinNorm2 = MODE == 0 ? 2e-12f : 0.f;  // MODE 0 counts surely-live slots only
-      const int row = wave * kRows + lane;
-      if (lane < kRows) {
-        sm.live[row] = h != 0 && (!mask || (bl & mask) == mask) && n2 > kMinNorm2 && start + row >= t * kTile;
-        sm.inv[row] = n2 > 0.f ? rsqrtf(n2) : 0.f;
-      }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    {
-      const f32x4* invp = (const f32x4*)(sm.inv + fq * 4 + sh * kBlk * 16);
-      const int4* livp = (const int4*)(sm.live + fq * 4 + sh * kBlk * 16);
-      float best[kNJ];
-#pragma unroll
-      for (int j = 0; j < kNJ; ++j) best[j] = -FLT_MAX;
-#pragma unroll
-      for (int i = 0; i < kBlk; ++i) {
-        const f32x4 iv = invp[i * 4];
-        const int4 lv = livp[i * 4];
-        const int lvr[4] = {lv.x, lv.y, lv.z, lv.w};
-#pragma unroll
-        for (int j = 0; j < kNJ; ++j)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float sim = acc[i][j][r] * iv[r];
-            if (MODE == 0) {
-              if (lvr[r]) best[j] = fmaxf(best[j], sim);
-            } else if (sim >= thr[j] && lvr[r]) {
-              const int q = (qtile0 + j) * 16 + fr;
-              const uint32_t p = atomicAdd(&sm.ncand[q], 1u);
-              if (p < (uint32_t)capb)
-                cand[((long)q * gridDim.x + blockIdx.x) * capb + p] = (uint32_t)(start + (sh * kBlk + i) * 16 + fq * 4 + r);
-            }
-          }
-      }
-      if (MODE == 0) {  // per query: max over the lane quads, then the two slot halves meet in LDS
-        float bj[kNJ];
-#pragma unroll
-        for (int j = 0; j < kNJ; ++j) {
-          bj[j] = fmaxf(best[j], __shfl_xor(best[j], 16, 64));
-          bj[j] = fmaxf(bj[j], __shfl_xor(bj[j], 32, 64));
-        }
-        if (sh == 1 && fq == 0)
-#pragma unroll
-          for (int j = 0; j < kNJ; ++j) sm.pmax[(qtile0 + j) * 16 + fr] = bj[j];
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        if (sh == 0 && fq == 0)
-#pragma unroll
-          for (int j = 0; j < kNJ; ++j) {
-            const int q = (qtile0 + j) * 16 + fr;
-            if (q < nq) bmax[(t - tile_base) * nq + q] = fmaxf(bj[j], sm.pmax[q]);
-          }
-      }
-    }
+  static __device__ __forceinline__ acc_t mfma(frag_t x, frag_t y, acc_t c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(x, y, c, 0, 0, 0);
   }
-  if (MODE == 1) {
-    mf::raw_barrier();
-    const int q = threadIdx.x;
-    if (q < nq && q < kQ) cnt[(long)q * gridDim.x + blockIdx.x] = sm.ncand[q];
+  template <int MODE>
+  static __device__ __forceinline__ Q queries(Lds&, const float2*, const float* thr_in, int nq, int,
+                                              int qtile0, int fr) {
+    Q q;
+#pragma unroll
+    for (int j = 0; j < kNJ; ++j) {
+      const int qi = (qtile0 + j) * 16 + fr;
+      q.thr[j] = (MODE == 1 && qi < nq) ? thr_in[qi] : FLT_MAX;
+    }
+    return q;
   }
-  mf::wait_vm0();
-}
-}  // namespace mf16
+  template <int MODE>
+  static __device__ __forceinline__ void put_row(Lds& l, int row, bool cand, meta_t n2) {
+    constexpr float kMinNorm2 = MODE == 0 ? 2e-12f : 0.f;  // MODE 0 counts surely-live slots only
+    l.live[row] = cand && n2 > kMinNorm2;
+    l.inv[row] = n2 > 0.f ? rsqrtf(n2) : 0.f;
+  }
+  static __device__ __forceinline__ const Q& epilogue_queries(const Lds&, const Q& q, int, int) { return q; }
+  static __device__ __forceinline__ Row get_rows(const Lds& l, int r0, int i) {  // rows r0 + 16i .. + 3
+    const int4 lv = ((const int4*)(l.live + r0))[i * 4];
+    return Row{((const f32x4*)(l.inv + r0))[i * 4], {lv.x, lv.y, lv.z, lv.w}};
+  }
+  // MODE 0: the live rows' maximum of sim into `best`; MODE 1: is (row r, query j) a candidate
+  template <int MODE>
+  static __device__ __forceinline__ bool score(float acc, const Row& w, int r, const Q& q, int j, float& best) {
+    const float sim = acc * w.iv[r];
+    if (MODE == 0) {
+      if (w.lv[r]) best = fmaxf(best, sim);
+      return false;
+    }
+    return sim >= q.thr[j] && w.lv[r];
+  }
+};
 
-// ---------------------------------------------------------------------------
-// The candidate pass on the side region's int8 copy (SPL_ARENA_VEC8 arenas, splinter_layout.hpp):
-// 768 B per slot, half the bf16 copy's bytes, on v_mfma_i32_16x16x64_i8.  A K-chunk of 64 dims is
-// 64 B per row, the byte geometry of mf16 (16-B fragment per lane over a 64-B row piece): the ring,
-// the DMA addressing and the rsw swizzle are mf16's, with 12 K-steps per tile instead of 24.  Lane
-// (fr, fq) holds bytes [16 fq, +16) of its row piece / query piece as the A / B fragment: both
-// operands put the same dims in the same lane group and byte, so the sum over k pairs them
-// whatever order the instruction walks k in.  The integer dot product is exact (|acc| <= 768 * 127^2
-// < 2^24, exact in fp32 too).
+// The integer dot product is exact (|acc| <= 768 * 127^2 < 2^24, exact in fp32 too).
 // With unit vectors q^, v^ and their dequantised forms q~ = cq qs, v~ = cv rs:
 //   |q^.v^ - q~.v~| <= |v^ - v~| + |q^ - q~| |v~| <= err + eq (1 + err),
 // so with approx = float(acc) rs qs and B = err + eq (1 + err) + 4e-4 + 2e-6 (4e-4: the real cosine
@@ -696,53 +586,110 @@ __global__ __launch_bounds__(kThreads, 1) void k_search_mma16(spl_arena_t aa, co
 //           of a real similarity, so the k-th largest tile maximum is the threshold itself;
 //   MODE 1: a live row is a candidate when approx + B >= thr[q], or when its vector cannot be
 //           bounded (err >= 2); rows without a vector (err < 0) never are.
-// In-order vmcnt: a wave issues per step (the metadata -- hash, bloom, the 8-B q8meta entry: 3
-// loads -- at step 0, then) the DMA of chunk s + 3, 2 query + 2 row pieces = 4.  Chunk s's DMA is
-// the last op of step s - 3 (for s < 3: of step s + 9 of the tile before, or of the prologue, which
-// issues chunks 0, 1, 2 back to back); younger than it at the top of step s are the two steps
-// between, 4 + 4 = 8, plus the 3 metadata loads when one of the two was a step 0 (s = 1, 2): 11.
-// In the first tile s = 0 has chunks 1, 2 behind chunk 0 (8), s = 1 has chunk 2 and step 0 (4 + 3 +
-// 4 = 11), s = 2 has steps 0 and 1 (3 + 4 + 4 = 11): the same counts.
-namespace mf8 {
-using mf::f32x4;
-using mf::rsrc_t;
-using mf::lds_void;
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-constexpr int kTile = mf::kTile, kQ = mf::kQ, kNJ = mf::kNJ;
-constexpr int kSteps = kD / 64;           // 12 K-chunks of 64 dims per tile
-constexpr int kWaves = 8, kThreads = kWaves * 64;  // two waves per SIMD
-constexpr int kChunk = kTile * 64;        // 16 KB of int8 slot rows per K-chunk
-constexpr int kQChunk = kQ * 64;          // 16 KB of int8 query fragments per K-chunk
-constexpr int kRing = mf::kRing, kAhead = mf::kAhead;
-constexpr int kRows = kTile / kWaves;     // slot rows a wave stages (DMA, metadata): 32
-constexpr int kBlk = 8;                   // 16-row blocks per wave: one slot half
-constexpr int kRsrcWord3 = mf::kRsrcWord3;
-constexpr float kSlack = 4e-4f + 2e-6f;
-static_assert(kSteps % kRing == 0 && kSteps > kAhead, "static ring slots across tiles");
-struct Smem {
-  char ring[kRing][kChunk];   // 64 KB
-  char qring[kRing][kQChunk]; // 64 KB
-  __attribute__((aligned(16))) float rs[kTile];
-  __attribute__((aligned(16))) float er[kTile];  // err of a live row, -1 for a row that does not count
-  uint32_t ncand[kQ];
-  float pmax[kQ];             // MODE 0: the upper slot half's per-query maxima
-  float2 qm[kQ];              // {qs, eq} per query, and MODE 1's thresholds: read in the epilogue only, so
-  float thr[kQ];              // they hold no registers across the K loop
+struct OpInt8 {
+  typedef i32x4 frag_t;
+  typedef i32x4 acc_t;
+  typedef float2 meta_t;                      // the row's {rs, err}
+  static constexpr int kSteps = kD / 64;      // K-chunks of 64 dims
+  static constexpr int kRowBytes = kD;
+  static constexpr int kMetaLoads = 3;        // hash, bloom, the 8-B q8meta[row]
+  static constexpr bool kCheckNq = true;
+  static constexpr float kSlack = 4e-4f + 2e-6f;
+  struct __attribute__((aligned(16))) Lds {
+    float rs[kTile];
+    float er[kTile];                          // err of a live row, -1 for a row that does not count
+    float2 qm[kQ];                            // {qs, eq} per query, and MODE 1's thresholds: read in the
+    float thr[kQ];                            // epilogue only, so they hold no registers across the K loop
+  };
+  struct Q {};
+  struct E { float thr[kNJ], qs[kNJ], eq[kNJ]; };
+  struct Row { f32x4 rv, ev; };
+  static __device__ __forceinline__ const void* rows(const spl::dev::Arena& a, long slot) { return a.vec8((size_t)slot); }
+  static __device__ __forceinline__ meta_t no_meta() { return make_float2(0.f, -1.f); }
+  static __device__ __forceinline__ meta_t load_meta(const spl::dev::Arena& a, long row) {
+    const uint64_t mw = __builtin_nontemporal_load((const uint64_t*)(a.q8meta() + row));
+    return make_float2(__builtin_bit_cast(float, (uint32_t)mw), __builtin_bit_cast(float, (uint32_t)(mw >> 32)));
+  }
+  static __device__ __forceinline__ acc_t mfma(frag_t x, frag_t y, acc_t c) {
+    return __builtin_amdgcn_mfma_i32_16x16x64_i8(x, y, c, 0, 0, 0);
+  }
+  // (visible to every wave after the first step's barrier; the epilogue reads them many barriers later)
+  template <int MODE>
+  static __device__ __forceinline__ Q queries(Lds& l, const float2* qmeta, const float* thr_in, int nq, int tid, int,
+                                              int) {
+    if (tid < kQ) {
+      l.qm[tid] = qmeta[tid];
+      l.thr[tid] = (MODE == 1 && tid < nq) ? thr_in[tid] : FLT_MAX;
+    }
+    return Q{};
+  }
+  template <int MODE>
+  static __device__ __forceinline__ void put_row(Lds& l, int row, bool cand, meta_t rm) {
+    l.rs[row] = rm.x;
+    l.er[row] = cand && rm.y >= 0.f ? rm.y : -1.f;
+  }
+  static __device__ __forceinline__ E epilogue_queries(const Lds& l, const Q&, int qtile0, int fr) {
+    E e;
+#pragma unroll
+    for (int j = 0; j < kNJ; ++j) {
+      const int q = (qtile0 + j) * 16 + fr;
+      e.thr[j] = l.thr[q];
+      e.qs[j] = l.qm[q].x;
+      e.eq[j] = l.qm[q].y;
+    }
+    return e;
+  }
+  static __device__ __forceinline__ Row get_rows(const Lds& l, int r0, int i) {
+    return Row{((const f32x4*)(l.rs + r0))[i * 4], ((const f32x4*)(l.er + r0))[i * 4]};
+  }
+  template <int MODE>
+  static __device__ __forceinline__ bool score(int acc, const Row& w, int r, const E& e, int j, float& best) {
+    const float approx = (float)acc * w.rv[r] * e.qs[j];
+    const float B = w.ev[r] + e.eq[j] * (1.f + w.ev[r]) + kSlack;
+    if (MODE == 0) {
+      if (w.ev[r] >= 0.f && w.rv[r] > 0.f) best = fmaxf(best, approx - B);
+      return false;
+    }
+    return w.ev[r] >= 0.f && (approx + B >= e.thr[j] || w.ev[r] >= 2.f);
+  }
 };
-using mf16::rsw;
 
-__device__ __forceinline__ rsrc_t tile_rsrc8(const spl::dev::Arena& a, long t, long slot_end) {
-  return __builtin_amdgcn_make_buffer_rsrc(a.vec8((size_t)mf::tile_start(t, slot_end)), 0, kTile * kD, kRsrcWord3);
+template <class Op>
+struct Smem {
+  char ring[kRing][kChunk];    // 64 KB
+  char qring[kRing][kQChunk];  // 64 KB
+  typename Op::Lds op;         // the tile's rows (and the queries) as the epilogue reads them
+  uint32_t ncand[kQ];
+  float pmax[kQ];              // MODE 0: the upper slot half's per-query maxima
+};
+
+template <class Op>
+__device__ __forceinline__ rsrc_t tile_rsrc(const spl::dev::Arena& a, long t, long slot_end) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(Op::rows(a, mf::tile_start(t, slot_end))), 0,
+                                           kTile * Op::kRowBytes, kRsrcWord3);
 }
 
-template <int MODE>
-__global__ __launch_bounds__(kThreads, 1) void k_search_mma8(spl_arena_t aa, const void* __restrict__ qf,
+// In-order vmcnt accounting, the reason the step waits below are right: a wave issues per step
+// (the row metadata, Op::kMetaLoads loads, at step 0, then) the DMA of chunk s + kAhead,
+// kDmaPerStep wave-instructions.  Chunk s's DMA is the last op of step s - 3 (for s < 3: of the
+// tile before, or of the prologue, which issues chunks 0, 1, 2 back to back); younger than it at the
+// top of step s are the two steps between, 2 kDmaPerStep, plus the metadata loads when one of the
+// two was a step 0 (s = 1, 2).  In the first tile s = 0 has chunks 1, 2 behind chunk 0, s = 1 has
+// chunk 2 and step 0, s = 2 has steps 0 and 1: the same counts.  The ring slots are static across
+// tiles because kSteps is a multiple of the ring depth.
+template <class Op, int MODE>  // MODE 0 = per-tile max per query, 1 = emit candidates
+__global__ __launch_bounds__(kThreads, 1) void k_search_side(spl_arena_t aa, const void* __restrict__ qf,
                                                             const float2* __restrict__ qmeta, int nq, long slot_begin,
                                                             long slot_end, uint64_t mask,
                                                             const float* __restrict__ thr_in, float* __restrict__ bmax,
                                                             uint32_t* __restrict__ cnt, uint32_t* __restrict__ cand,
                                                             int capb) {
-  __shared__ __attribute__((aligned(16))) Smem sm;
+  constexpr int kSteps = Op::kSteps;
+  static_assert(kSteps % kRing == 0 && kSteps > kAhead, "static ring slots across tiles");
+  static_assert(kAhead == 3, "the step waits count the two steps between a chunk's DMA and its use");
+  typedef typename Op::frag_t frag_t;
+  typedef typename Op::acc_t acc_t;
+  __shared__ __attribute__((aligned(16))) Smem<Op> sm;
   const spl::dev::Arena a = spl::dev::from_api(aa);
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int fr = lane & 15, fq = lane >> 4;
@@ -753,7 +700,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_search_mma8(spl_arena_t aa, con
   if (t0 >= tile_end) return;  // block-uniform
   if (MODE == 1 && tid < kQ) sm.ncand[tid] = 0;
 
-  const rsrc_t qr = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(qf), 0, kQ * kD, kRsrcWord3);
+  const rsrc_t qr = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(qf), 0, kQ * Op::kRowBytes, kRsrcWord3);
   const int qtile0 = qg * kNJ;
   // row DMA: wave-instruction k of a chunk fills rows 32w + 16k .. +16 (1 KB), lane l -> row +(l >> 2),
   // physical unit l & 3 <- logical unit (l & 3) ^ rsw(row & 15); query DMA: instruction k brings the
@@ -762,16 +709,12 @@ __global__ __launch_bounds__(kThreads, 1) void k_search_mma8(spl_arena_t aa, con
 #pragma unroll
   for (int k = 0; k < 2; ++k) {
     const int row = wave * kRows + k * 16 + (lane >> 2);
-    dvoff[k] = row * kD + (((lane & 3) ^ rsw(row & 15)) << 4);
+    dvoff[k] = row * Op::kRowBytes + (((lane & 3) ^ rsw(row & 15)) << 4);
   }
-  const float2* q8m = a.q8meta();
   // fragment read: row 16i + fr of this wave's slot half, logical unit fq
   const int rdo = fr * 64 + ((fq ^ rsw(fr)) << 4) + sh * kBlk * 1024;
 
-  if (tid < kQ) {
-    sm.qm[tid] = qmeta[tid];
-    sm.thr[tid] = (MODE == 1 && tid < nq) ? thr_in[tid] : FLT_MAX;
-  }
+  const auto qv = Op::template queries<MODE>(sm.op, qmeta, thr_in, nq, tid, qtile0, fr);
   auto issue = [&](rsrc_t er, int c, int slot) {
 #pragma unroll
     for (int k = 0; k < 2; ++k)
@@ -783,111 +726,89 @@ __global__ __launch_bounds__(kThreads, 1) void k_search_mma8(spl_arena_t aa, con
       __builtin_amdgcn_raw_ptr_buffer_load_lds(er, (lds_void*)(dst + k * 1024), 16, dvoff[k], c * 64, 0, 0);
   };
   const long last = tile_end - 1;
-  // (visible to every wave after the first step's barrier; the epilogue reads them many barriers later)
   {
-    const rsrc_t er = tile_rsrc8(a, t0, slot_end);
+    const rsrc_t er = tile_rsrc<Op>(a, t0, slot_end);
     for (int c = 0; c < kAhead; ++c) issue(er, c, c);
   }
 
   for (long t = t0; t < tile_end; t += G) {
     const long start = mf::tile_start(t, slot_end);
-    const rsrc_t er_cur = tile_rsrc8(a, t, slot_end);
-    const rsrc_t er_next = tile_rsrc8(a, t + G < tile_end ? t + G : last, slot_end);
+    // the stream runs one tile ahead at the end of a tile (the last tile re-reads itself: in bounds, unused)
+    const rsrc_t er_cur = tile_rsrc<Op>(a, t, slot_end);
+    const rsrc_t er_next = tile_rsrc<Op>(a, t + G < tile_end ? t + G : last, slot_end);
     uint64_t h = 0, bl = 0;
-    float2 rm = make_float2(0.f, -1.f);
-    i32x4 acc[kBlk][kNJ];
+    typename Op::meta_t rm = Op::no_meta();
+    acc_t acc[kBlk][kNJ];
 #pragma unroll
     for (int i = 0; i < kBlk; ++i)
 #pragma unroll
-      for (int j = 0; j < kNJ; ++j) acc[i][j] = i32x4{0, 0, 0, 0};
+      for (int j = 0; j < kNJ; ++j) acc[i][j] = acc_t{0, 0, 0, 0};
 
 #pragma clang loop unroll(full)
     for (int s = 0; s < kSteps; ++s) {
+      // chunk s landed (this wave's DMA) and, after the barrier, every wave's DMA landed and every
+      // wave is done with chunk s - 1's ring buffer
       if (s == 1 || s == 2)
-        SPL_STEP_SYNC(11);
+        mf::step_sync<2 * kDmaPerStep + Op::kMetaLoads>();
       else
-        SPL_STEP_SYNC(8);
+        mf::step_sync<2 * kDmaPerStep>();
       if (s == 0) {  // metadata of this wave's 32 rows (lanes 32-63 repeat 0-31)
         const long row = start + wave * kRows + (lane & (kRows - 1));
         const uint8_t* sp = a.slot((size_t)row);
         h = __builtin_nontemporal_load((const uint64_t*)(sp + spl::kOffHash));
         bl = __builtin_nontemporal_load((const uint64_t*)(sp + spl::kOffBloom));
-        const uint64_t mw = __builtin_nontemporal_load((const uint64_t*)(q8m + row));
-        rm = make_float2(__builtin_bit_cast(float, (uint32_t)mw), __builtin_bit_cast(float, (uint32_t)(mw >> 32)));
+        rm = Op::load_meta(a, row);
       }
-      const char* qsp = sm.qring[s % kRing] + lane * 16;
-      i32x4 bq[kNJ];
+      const char* qs = sm.qring[s % kRing] + lane * 16;
+      frag_t bq[kNJ];
 #pragma unroll
-      for (int j = 0; j < kNJ; ++j) bq[j] = *(const i32x4*)(qsp + (qtile0 + j) * 1024);
+      for (int j = 0; j < kNJ; ++j) bq[j] = *(const frag_t*)(qs + (qtile0 + j) * 1024);
       const char* ch = sm.ring[s % kRing] + rdo;
 #pragma unroll
       for (int i0 = 0; i0 < kBlk; i0 += 4) {
-        i32x4 af[4];
+        frag_t af[4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) af[u] = *(const i32x4*)(ch + (i0 + u) * 1024);
+        for (int u = 0; u < 4; ++u) af[u] = *(const frag_t*)(ch + (i0 + u) * 1024);
 #pragma unroll
         for (int u = 0; u < 4; ++u)
 #pragma unroll
-          for (int j = 0; j < kNJ; ++j)
-            acc[i0 + u][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[u], bq[j], acc[i0 + u][j], 0, 0, 0);
-        // the next chunk's DMA after the first MFMA group, as in mf16
+          for (int j = 0; j < kNJ; ++j) acc[i0 + u][j] = Op::mfma(af[u], bq[j], acc[i0 + u][j]);
+        // the next chunk's DMA after the first MFMA group: its issue overlaps matrix work (11.92 vs
+        // 12.15 ms per pass issued before the group; s_setprio around the groups: neutral)
         if (i0 == 0) issue(s + kAhead < kSteps ? er_cur : er_next, (s + kAhead) % kSteps, (s + kAhead) % kRing);
       }
     }
-    {
+    if (lane < kRows) {
       const int row = wave * kRows + lane;
-      if (lane < kRows) {
-        const bool live = h != 0 && (!mask || (bl & mask) == mask) && start + row >= t * kTile && rm.y >= 0.f;
-        sm.rs[row] = rm.x;
-        sm.er[row] = live ? rm.y : -1.f;
-      }
+      Op::template put_row<MODE>(sm.op, row, h != 0 && (!mask || (bl & mask) == mask) && start + row >= t * kTile, rm);
     }
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    mf::lds_barrier();
     {
-      const f32x4* rsp = (const f32x4*)(sm.rs + fq * 4 + sh * kBlk * 16);  // rows 16i + 4fq + r, r = 0..3
-      const f32x4* erp = (const f32x4*)(sm.er + fq * 4 + sh * kBlk * 16);
-      float best[kNJ], thr[kNJ], qs[kNJ], eq[kNJ];
+      const auto& qe = Op::epilogue_queries(sm.op, qv, qtile0, fr);
+      float best[kNJ];
 #pragma unroll
-      for (int j = 0; j < kNJ; ++j) {
-        const int q = (qtile0 + j) * 16 + fr;
-        best[j] = -FLT_MAX;
-        thr[j] = sm.thr[q];
-        qs[j] = sm.qm[q].x;
-        eq[j] = sm.qm[q].y;
-      }
+      for (int j = 0; j < kNJ; ++j) best[j] = -FLT_MAX;
 #pragma unroll
       for (int i = 0; i < kBlk; ++i) {
-        const f32x4 rv = rsp[i * 4];
-        const f32x4 ev = erp[i * 4];
+        const auto w = Op::get_rows(sm.op, sh * kBlk * 16 + fq * 4, i);  // rows 16i + 4fq + r, r = 0..3 of the half
 #pragma unroll
         for (int j = 0; j < kNJ; ++j)
 #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float approx = (float)acc[i][j][r] * rv[r] * qs[j];
-            const float B = ev[r] + eq[j] * (1.f + ev[r]) + kSlack;
-            if (MODE == 0) {
-              if (ev[r] >= 0.f && rv[r] > 0.f) best[j] = fmaxf(best[j], approx - B);
-            } else if (ev[r] >= 0.f && (approx + B >= thr[j] || ev[r] >= 2.f)) {
+          for (int r = 0; r < 4; ++r)
+            if (Op::template score<MODE>(acc[i][j][r], w, r, qe, j, best[j])) {
               const int q = (qtile0 + j) * 16 + fr;
-              if (q < nq) {
-                const uint32_t p = atomicAdd(&sm.ncand[q], 1u);
-                if (p < (uint32_t)capb)
-                  cand[((long)q * gridDim.x + blockIdx.x) * capb + p] = (uint32_t)(start + (sh * kBlk + i) * 16 + fq * 4 + r);
-              }
+              if (!Op::kCheckNq || q < nq)
+                mf::emit_cand(sm.ncand, cand, q, capb, (uint32_t)(start + (sh * kBlk + i) * 16 + fq * 4 + r));
             }
-          }
       }
       if (MODE == 0) {  // per query: max over the lane quads, then the two slot halves meet in LDS
         float bj[kNJ];
 #pragma unroll
-        for (int j = 0; j < kNJ; ++j) {
-          bj[j] = fmaxf(best[j], __shfl_xor(best[j], 16, 64));
-          bj[j] = fmaxf(bj[j], __shfl_xor(bj[j], 32, 64));
-        }
+        for (int j = 0; j < kNJ; ++j) bj[j] = mf::quad_max(best[j]);
         if (sh == 1 && fq == 0)
 #pragma unroll
           for (int j = 0; j < kNJ; ++j) sm.pmax[(qtile0 + j) * 16 + fr] = bj[j];
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        mf::lds_barrier();
         if (sh == 0 && fq == 0)
 #pragma unroll
           for (int j = 0; j < kNJ; ++j) {
@@ -902,9 +823,9 @@ __global__ __launch_bounds__(kThreads, 1) void k_search_mma8(spl_arena_t aa, con
     const int q = threadIdx.x;
     if (q < nq && q < kQ) cnt[(long)q * gridDim.x + blockIdx.x] = sm.ncand[q];
   }
-  mf::wait_vm0();
+  mf::wait_vm0();  // drain the trailing DMAs (next-tile prefetch of the last tile) before the LDS goes away
 }
-}  // namespace mf8
+}  // namespace side
 
 namespace mf {
 // fp32 re-score of the candidates of one query (block) and top-K selection;
@@ -1087,38 +1008,56 @@ __global__ __launch_bounds__(256) void k_score_all(spl_arena_t aa, const float* 
 }  // namespace
 
 // ---------------------------------------------------------- query prep --
-// The batched search's query operand on the device (was a host loop per 256-query block): one
-// workgroup per query slot of the 256-query block -- L2 norm (fp32 sum of squares over the wave
-// reduction), normalised, rounded to bf16, stored in the candidate pass's fragment order
-// [16 q-tiles][24 steps][4 kq][16 r][8]: dims [32 step + 8 kq, +8) of query 16 tile + r.  Query
-// slots >= n are zero.
-__global__ __launch_bounds__(256) void k_search_qprep(const float* __restrict__ q, int n, uint16_t* __restrict__ qf) {
-  const int qi = blockIdx.x, t = threadIdx.x;
-  __shared__ float red[4];
-  float v[3] = {0.f, 0.f, 0.f};
-  if (qi < n) {
+// The batched search's query operands on the device (was a host loop per 256-query block): one
+// workgroup per query slot of the 256-query block, thread t holds dims t, t + 256, t + 512.
+// Both operands are stored in the candidate pass's fragment order [16 q-tiles][steps][4 kq][16 r][F],
+// F elements per 16-B lane fragment (8 bf16, 16 int8) and 768 / 4F steps: dims [4F step + F kq, +F)
+// of query 16 tile + r.  qfrag_off: the element index of dim d of query slot qi.
+template <int F>
+constexpr long qfrag_off(int qi, int d) {
+  return ((((long)(qi >> 4) * (kD / (4 * F)) + d / (4 * F)) * 4 + (d / F) % 4) * 16 + (qi & 15)) * F + d % F;
+}
+// block sum of ss (and, with MAX, block maximum of m) over 256 threads through red[.][4]
+template <bool MAX>
+__device__ __forceinline__ void qprep_reduce(float& ss, float& m, float (*red)[4]) {
+  const int t = threadIdx.x;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) v[c] = q[(long)qi * 768 + t + 256 * c];
+  for (int o = 32; o > 0; o >>= 1) {
+    ss += __shfl_xor(ss, o, 64);
+    if (MAX) m = fmaxf(m, __shfl_xor(m, o, 64));
   }
-  float ss = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
-  if ((t & 63) == 0) red[t >> 6] = ss;
+  if ((t & 63) == 0) {
+    red[0][t >> 6] = ss;
+    if (MAX) red[1][t >> 6] = m;
+  }
   __syncthreads();
-  const float tot = red[0] + red[1] + red[2] + red[3];
-  const float inv = tot > 1e-30f ? rsqrtf(tot) : 0.f;
-  const int tile = qi >> 4, r = qi & 15;
+  ss = red[0][0] + red[0][1] + red[0][2] + red[0][3];
+  if (MAX) m = fmaxf(fmaxf(red[1][0], red[1][1]), fmaxf(red[1][2], red[1][3]));
+}
+// this thread's three dims of query slot qi (zeros for a slot >= n), the query's sum of squares
+// and, with MAX, its largest magnitude
+template <bool MAX>
+__device__ __forceinline__ void qprep_load(const float* __restrict__ q, int qi, int n, float (&v)[3], float& ss,
+                                           float& m, float (*red)[4]) {
 #pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const int d = t + 256 * c;
-    const int st = d >> 5, kq = (d >> 3) & 3, e = d & 7;
-    qf[((((long)tile * 24 + st) * 4 + kq) * 16 + r) * 8 + e] = __builtin_bit_cast(uint16_t, (__bf16)(v[c] * inv));
-  }
+  for (int c = 0; c < 3; ++c) v[c] = qi < n ? q[(long)qi * kD + threadIdx.x + 256 * c] : 0.f;
+  ss = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
+  m = fmaxf(fabsf(v[0]), fmaxf(fabsf(v[1]), fabsf(v[2])));
+  qprep_reduce<MAX>(ss, m, red);
 }
 
-// The int8 candidate pass's query operand: one workgroup per query slot of the 256-query block --
-// the codes c = rint(q 127 / max|q|) in fragment order [16 q-tiles][12 steps][4 kq][16 r][16 B]
-// (dims [64 step + 16 kq, +16) of query 16 tile + r) and qmeta {qs, eq}, defined as the rows'
+// bf16 operand: L2 norm (fp32 sum of squares), normalised, rounded to bf16.  Query slots >= n are zero.
+__global__ __launch_bounds__(256) void k_search_qprep(const float* __restrict__ q, int n, uint16_t* __restrict__ qf) {
+  const int qi = blockIdx.x, t = threadIdx.x;
+  __shared__ float red[1][4];
+  float v[3], tot, m;
+  qprep_load<false>(q, qi, n, v, tot, m, red);
+  const float inv = tot > 1e-30f ? rsqrtf(tot) : 0.f;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) qf[qfrag_off<8>(qi, t + 256 * c)] = __builtin_bit_cast(uint16_t, (__bf16)(v[c] * inv));
+}
+
+// int8 operand: the codes c = rint(q 127 / max|q|) and qmeta {qs, eq}, defined as the rows'
 // {rs, err} (arena_dev.hpp write_vec8_wave).  Query slots >= n: zeros and {0, -1}; a query without
 // a usable norm (zero, not finite): zeros and {0, 2} -- every live row becomes its candidate and
 // the exact kernel answers it.
@@ -1127,44 +1066,22 @@ __global__ __launch_bounds__(256) void k_search_qprep8(const float* __restrict__
   using namespace spl::dev;
   const int qi = blockIdx.x, t = threadIdx.x;
   __shared__ float red[3][4];
-  float v[3] = {0.f, 0.f, 0.f};
-  if (qi < n) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) v[c] = q[(long)qi * 768 + t + 256 * c];
-  }
-  float ss = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
-  float m = fmaxf(fabsf(v[0]), fmaxf(fabsf(v[1]), fabsf(v[2])));
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    ss += __shfl_xor(ss, o, 64);
-    m = fmaxf(m, __shfl_xor(m, o, 64));
-  }
-  if ((t & 63) == 0) { red[0][t >> 6] = ss; red[1][t >> 6] = m; }
-  __syncthreads();
-  ss = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-  m = fmaxf(fmaxf(red[1][0], red[1][1]), fmaxf(red[1][2], red[1][3]));
+  float v[3], ss, m;
+  qprep_load<true>(q, qi, n, v, ss, m, red);
   float qsv = 0.f;
   const float sc = qi < n ? q8_scale(ss, m, &qsv) : 0.f;
   const float inv = sc != 0.f ? 1.f / sqrtf(ss) : 0.f;
-  const int tile = qi >> 4, r = qi & 15;
   float es = 0.f;
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
-    const int d = t + 256 * c;
-    const int st = d >> 6, kq = (d >> 4) & 3, e = d & 15;
     const int code = sc != 0.f ? q8_code(v[c], sc) : 0;
     const float df = v[c] * inv - (float)code * qsv;
     es += sc != 0.f ? df * df : 0.f;
-    qf[((((long)tile * 12 + st) * 4 + kq) * 16 + r) * 16 + e] = (int8_t)code;
+    qf[qfrag_off<16>(qi, t + 256 * c)] = (int8_t)code;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) es += __shfl_xor(es, o, 64);
-  if ((t & 63) == 0) red[2][t >> 6] = es;
-  __syncthreads();
-  if (t == 0) {
-    es = red[2][0] + red[2][1] + red[2][2] + red[2][3];
+  qprep_reduce<false>(es, m, red + 2);
+  if (t == 0)
     qmeta[qi] = qi >= n ? make_float2(0.f, -1.f) : sc != 0.f ? make_float2(qsv, q8_err(es)) : make_float2(0.f, 2.f);
-  }
 }
 
 // slot cores (128 B) of a result list, gathered on the device so the hits leave with their keys
@@ -1194,6 +1111,37 @@ __global__ __launch_bounds__(256) void k_search_over(const uint32_t* __restrict_
   if (threadIdx.x == 0) over[qi] = o ? 1u : 0u;
 }
 
+// which operand the batched search uses on this arena (search_api.h); the environment is read per
+// call so that one process can compare the paths
+static int pick_copy(spl_arena_t a) {
+  if (a.stride != 3200) return SPL_SEARCH_COPY_FP32;
+  const char* e8 = getenv("SPLINTER_SEARCH_VEC8");
+  if ((a.flags & SPL_ARENA_VEC8) && !(e8 && e8[0] == '0')) return SPL_SEARCH_COPY_INT8;
+  const char* e16 = getenv("SPLINTER_SEARCH_VEC16");
+  if ((a.flags & SPL_ARENA_VEC16) && !(e16 && e16[0] == '0')) return SPL_SEARCH_COPY_BF16;
+  return SPL_SEARCH_COPY_FP32;
+}
+
+// The arguments of a candidate pass, checked once for every operand: the grid to launch, 0 for an
+// invalid call.  MODE 0 needs no more blocks than tiles; in MODE 1 every one of the `grid` segments
+// per query is read, so no clamping (blocks without a tile leave the zeroed count).
+static int pass_grid(spl_arena_t a, const void* qop, int nq, long slot_begin, long slot_end, int mode, const float* thr,
+                     const float* bmax, const uint32_t* cnt, const uint32_t* cand, int capb, int grid) {
+  if (a.stride != 3200 || !qop || nq <= 0 || nq > mf::kQ || slot_begin < 0 || slot_begin % mf::kTile ||
+      slot_end > (long)a.slots || slot_end - slot_begin < mf::kTile || (mode != 0 && mode != 1) || grid <= 0 ||
+      (mode == 1 && (!thr || !cnt || !cand || capb <= 0)) || (mode == 0 && !bmax))
+    return 0;
+  const long tiles = (slot_end - slot_begin + mf::kTile - 1) / mf::kTile;
+  return mode == 0 && tiles < grid ? (int)tiles : grid;
+}
+
+template <class K, class... A>
+static int launch_pass(K k0, K k1, int mode, int grid, int threads, hipStream_t s, A... args) {
+  if (grid <= 0) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(mode == 0 ? k0 : k1, dim3(grid), dim3(threads), 0, s, args...);
+  return (int)hipGetLastError();
+}
+
 extern "C" {
 
 int spl_arena_score_all(spl_arena_t a, const float* query, float min_sim, float max_dist, uint64_t mask, void* out,
@@ -1221,36 +1169,16 @@ int spl_search_qprep8(const float* queries, int nq, void* qfrag8, void* qmeta, h
   return (int)hipGetLastError();
 }
 
-// which operand the batched search uses on this arena (search_api.h); the environment is read per
-// call so that one process can compare the paths
-int spl_search_copy_kind(spl_arena_t a) {
-  if (a.stride != 3200) return SPL_SEARCH_COPY_FP32;
-  const char* e8 = getenv("SPLINTER_SEARCH_VEC8");
-  if ((a.flags & SPL_ARENA_VEC8) && !(e8 && e8[0] == '0')) return SPL_SEARCH_COPY_INT8;
-  const char* e16 = getenv("SPLINTER_SEARCH_VEC16");
-  if ((a.flags & SPL_ARENA_VEC16) && !(e16 && e16[0] == '0')) return SPL_SEARCH_COPY_BF16;
-  return SPL_SEARCH_COPY_FP32;
-}
+int spl_search_copy_kind(spl_arena_t a) { return pick_copy(a); }
 
 int spl_search_mma_pass8(spl_arena_t a, const void* qfrag8, const void* qmeta, int nq, long slot_begin, long slot_end,
                          uint64_t mask, int mode, const float* thr, float* bmax, uint32_t* cnt, uint32_t* cand,
                          int capb, int grid, hipStream_t s) {
-  if (a.stride != 3200 || !(a.flags & SPL_ARENA_VEC8) || !qfrag8 || !qmeta || nq <= 0 || nq > mf::kQ ||
-      slot_begin < 0 || slot_begin % mf::kTile || slot_end > (long)a.slots || slot_end - slot_begin < mf::kTile ||
-      (mode != 0 && mode != 1) || grid <= 0 || (mode == 1 && (!thr || !cnt || !cand || capb <= 0)) ||
-      (mode == 0 && !bmax))
-    return (int)hipErrorInvalidValue;
-  const long tiles = (slot_end - slot_begin + mf::kTile - 1) / mf::kTile;
-  if (mode == 0) {
-    const int g = (int)(grid < tiles ? grid : tiles);
-    hipLaunchKernelGGL(mf8::k_search_mma8<0>, dim3(g), dim3(mf8::kThreads), 0, s, a, qfrag8, (const float2*)qmeta, nq,
-                       slot_begin, slot_end, mask, thr, bmax, cnt, cand, capb);
-  } else {
-    // every one of the `grid` segments per query is read: blocks without a tile leave the zeroed count
-    hipLaunchKernelGGL(mf8::k_search_mma8<1>, dim3(grid), dim3(mf8::kThreads), 0, s, a, qfrag8, (const float2*)qmeta, nq,
-                       slot_begin, slot_end, mask, thr, bmax, cnt, cand, capb);
-  }
-  return (int)hipGetLastError();
+  const bool ok = (a.flags & SPL_ARENA_VEC8) && qmeta;
+  const int g = ok ? pass_grid(a, qfrag8, nq, slot_begin, slot_end, mode, thr, bmax, cnt, cand, capb, grid) : 0;
+  return launch_pass(side::k_search_side<side::OpInt8, 0>, side::k_search_side<side::OpInt8, 1>, mode, g,
+                     side::kThreads, s, a, qfrag8, (const float2*)qmeta, nq, slot_begin, slot_end, mask, thr, bmax, cnt,
+                     cand, capb);
 }
 
 int spl_search_cores(spl_arena_t a, const void* result, int n, void* out_cores, hipStream_t s) {
@@ -1286,37 +1214,17 @@ int spl_search_mma_tile() { return mf::kTile; }
 int spl_search_mma_pass(spl_arena_t a, const void* qfrag, int nq, long slot_begin, long slot_end, uint64_t mask,
                         int mode, const float* thr, float* bmax, uint32_t* cnt, uint32_t* cand, int capb, int grid,
                         hipStream_t s) {
-  if (a.stride != 3200 || nq <= 0 || nq > mf::kQ || slot_begin < 0 || slot_begin % mf::kTile ||
-      slot_end > (long)a.slots || slot_end - slot_begin < mf::kTile || (mode != 0 && mode != 1) || grid <= 0 ||
-      (mode == 1 && (!thr || !cnt || !cand || capb <= 0)) || (mode == 0 && !bmax))
-    return (int)hipErrorInvalidValue;
-  const long tiles = (slot_end - slot_begin + mf::kTile - 1) / mf::kTile;
-  // the bf16 copy when the arena carries one (SPLINTER_SEARCH_VEC16=0: the fp32 rows)
-  static const bool v16_ok = [] {
-    const char* e = getenv("SPLINTER_SEARCH_VEC16");
-    return !(e && e[0] == '0');
-  }();
-  if ((a.flags & SPL_ARENA_VEC16) && v16_ok) {
-    const int g = mode == 0 ? (int)(grid < tiles ? grid : tiles) : grid;
-    if (mode == 0)
-      hipLaunchKernelGGL(mf16::k_search_mma16<0>, dim3(g), dim3(mf16::kThreads), 0, s, a, qfrag, nq, slot_begin,
-                         slot_end, mask, thr, bmax, cnt, cand, capb);
-    else
-      hipLaunchKernelGGL(mf16::k_search_mma16<1>, dim3(g), dim3(mf16::kThreads), 0, s, a, qfrag, nq, slot_begin,
-                         slot_end, mask, thr, bmax, cnt, cand, capb);
-    return (int)hipGetLastError();
-  }
-  if (mode == 0) {
-    const int g = (int)(grid < tiles ? grid : tiles);
-    hipLaunchKernelGGL(mf::k_search_mma<0>, dim3(g), dim3(mf::kThreads), 0, s, a, qfrag, nq, slot_begin, slot_end,
-                       mask, thr, bmax, cnt, cand, capb);
-  } else {
-    // every one of the `grid` segments per query must be written: no clamping to the tile count
-    // (blocks without a tile store a zero count)
-    hipLaunchKernelGGL(mf::k_search_mma<1>, dim3(grid), dim3(mf::kThreads), 0, s, a, qfrag, nq, slot_begin, slot_end,
-                       mask, thr, bmax, cnt, cand, capb);
-  }
-  return (int)hipGetLastError();
+  const int g = pass_grid(a, qfrag, nq, slot_begin, slot_end, mode, thr, bmax, cnt, cand, capb, grid);
+  // the bf16 copy when the arena carries one (SPLINTER_SEARCH_VEC16=0: the fp32 rows); this pass never
+  // streams the int8 copy
+  spl_arena_t no8 = a;
+  no8.flags &= ~(uint32_t)SPL_ARENA_VEC8;
+  if (pick_copy(no8) == SPL_SEARCH_COPY_BF16)
+    return launch_pass(side::k_search_side<side::OpBf16, 0>, side::k_search_side<side::OpBf16, 1>, mode, g,
+                       side::kThreads, s, a, qfrag, (const float2*)nullptr, nq, slot_begin, slot_end, mask, thr, bmax,
+                       cnt, cand, capb);
+  return launch_pass(mf::k_search_mma<0>, mf::k_search_mma<1>, mode, g, mf::kThreads, s, a, qfrag, nq, slot_begin,
+                     slot_end, mask, thr, bmax, cnt, cand, capb);
 }
 
 int spl_search_thr(const float* bmax, int tiles, int nq, int K, float delta2, float floor_v, float* thr,

@@ -35,8 +35,10 @@ int spl_search_qprep(const float *queries, int nq, void *qfrag, hipStream_t stre
 
 /* The int8 candidate pass (SPL_ARENA_VEC8 arenas, splinter_layout.hpp).  spl_search_copy_kind: the
  * operand the batched search should use on this arena now -- the int8 copy when the arena has one
- * (SPLINTER_SEARCH_VEC8=0, read per call: ignore it), else the bf16 copy (SPLINTER_SEARCH_VEC16=0:
- * ignore it), else the fp32 rows.  Hosts pick the query operand and the threshold margin by it. */
+ * (SPLINTER_SEARCH_VEC8=0: ignore it), else the bf16 copy (SPLINTER_SEARCH_VEC16=0: ignore it), else
+ * the fp32 rows.  Both variables are read on every call, here and in spl_search_mma_pass, by the same
+ * function: the operand named is the operand streamed.  Hosts pick the query operand and the
+ * threshold margin by it. */
 #define SPL_SEARCH_COPY_FP32 0
 #define SPL_SEARCH_COPY_BF16 1
 #define SPL_SEARCH_COPY_INT8 2

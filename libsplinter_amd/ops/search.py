@@ -133,30 +133,15 @@ class VectorSearch:
         for b in range(0, q.shape[0], MMA_Q):
             qq = q[b: b + MMA_Q]
             n = qq.shape[0]
-            qpad = MMA_Q
-            if i8:
-                qf, qmeta = self.qprep8(qq)
-            else:
-                qb = torch.zeros(qpad, 768, dtype=torch.bfloat16, device="cuda")
-                qb[:n] = (qq / qq.norm(dim=1, keepdim=True).clamp_min(1e-30)).to(torch.bfloat16)
-                # fragment order [q/16][24 steps][4 kq][16 r][8]: lane 16*kq + r of a wave load
-                qf = qb.view(qpad // 16, 16, 24, 4, 8).permute(0, 2, 3, 1, 4).contiguous()
-
-            def mma_pass(end, mode, thr_p, bmax_p, cnt_p, cand_p, cb):
-                if i8:
-                    return self.L.spl_search_mma_pass8(self.arena.desc, qf.data_ptr(), qmeta.data_ptr(), n, 0, end,
-                                                       label_mask, mode, thr_p, bmax_p, cnt_p, cand_p, cb, MMA_GRID, st)
-                return self.L.spl_search_mma_pass(self.arena.desc, qf.data_ptr(), n, 0, end, label_mask, mode,
-                                                  thr_p, bmax_p, cnt_p, cand_p, cb, MMA_GRID, st)
+            qop = self.qprep8(qq) if i8 else (self.qprep16(qq),)
+            pk = "int8" if i8 else "bf16"
 
             floor = torch.full((n,), float(min_sim) - delta, device="cuda")
             if bounded:
                 thr = floor
             else:
                 bmax = torch.empty(sample // TILE, n, dtype=torch.float32, device="cuda")
-                rc = mma_pass(sample, 0, None, bmax.data_ptr(), None, None, 0)
-                if rc != 0:
-                    raise RuntimeError(f"spl_search_mma_pass(bmax) failed ({rc})")
+                self.mma_pass(pk, qop, n, sample, 0, label_mask, bmax=bmax)
                 kk = min(k, bmax.shape[0])
                 kth = bmax.topk(kk, dim=0).values[-1]
                 if kk < k:
@@ -165,9 +150,7 @@ class VectorSearch:
                 thr = torch.maximum(kth if i8 else kth - 2 * DELTA, floor)
             cnt = torch.zeros(n, MMA_GRID, dtype=torch.int32, device="cuda")
             cand = torch.empty(n * MMA_GRID * capb, dtype=torch.int32, device="cuda")
-            rc = mma_pass(slots, 1, thr.data_ptr(), None, cnt.data_ptr(), cand.data_ptr(), capb)
-            if rc != 0:
-                raise RuntimeError(f"spl_search_mma_pass(cand) failed ({rc})")
+            self.mma_pass(pk, qop, n, slots, 1, label_mask, thr=thr, cnt=cnt, cand=cand, capb=capb)
             res = torch.empty(n * k * 4, dtype=torch.int32, device="cuda")
             rc = self.L.spl_search_rescore(self.arena.desc, qq.data_ptr(), n, k, float(min_sim), float(max_dist),
                                            label_mask, cnt.data_ptr(), cand.data_ptr(), MMA_GRID, capb,
@@ -207,17 +190,38 @@ class VectorSearch:
             raise RuntimeError(f"spl_search_qprep8 failed ({rc})")
         return qf, qmeta
 
+    def qprep16(self, queries: torch.Tensor) -> torch.Tensor:
+        """queries [n <= 256, 768] fp32 -> the bf16 pass's operand: L2-normalised, bf16, zero-padded to
+        256 queries, in fragment order [q/16][24 steps][4 kq][16 r][8] (lane 16*kq + r of a wave load)."""
+        q = queries.to(device="cuda", dtype=torch.float32).reshape(-1, 768)
+        if not 1 <= q.shape[0] <= MMA_Q:
+            raise ValueError(f"1..{MMA_Q} queries per block")
+        qb = torch.zeros(MMA_Q, 768, dtype=torch.bfloat16, device="cuda")
+        qb[:q.shape[0]] = (q / q.norm(dim=1, keepdim=True).clamp_min(1e-30)).to(torch.bfloat16)
+        return qb.view(MMA_Q // 16, 16, 24, 4, 8).permute(0, 2, 3, 1, 4).contiguous()
+
+    def mma_pass(self, kind: str, qop, nq: int, slot_end: int, mode: int, label_mask: int = 0, *,
+                 thr: Optional[torch.Tensor] = None, bmax: Optional[torch.Tensor] = None,
+                 cnt: Optional[torch.Tensor] = None, cand: Optional[torch.Tensor] = None, capb: int = 0,
+                 grid: int = MMA_GRID) -> None:
+        """One raw MFMA pass over slots [0, slot_end) (search_api.h spl_search_mma_pass / _pass8) for
+        the first `nq` queries of `qop`: ``kind`` "int8" with qop = qprep8's (codes, qmeta), or "bf16"
+        with qop = (qprep16's fragment,) -- on the bf16 copy, or the fp32 rows of an arena without one.
+        mode 0 fills bmax [tiles, nq]; mode 1 appends to cand [nq, grid, capb] and counts in the
+        zeroed cnt [nq, grid]."""
+        p = [t.data_ptr() if t is not None else None for t in (thr, bmax, cnt, cand)]
+        fn = {"int8": self.L.spl_search_mma_pass8, "bf16": self.L.spl_search_mma_pass}[kind]
+        rc = fn(self.arena.desc, *(t.data_ptr() for t in qop), nq, 0, slot_end, label_mask, mode, *p, capb, grid,
+                torch.cuda.current_stream().cuda_stream)
+        if rc != 0:
+            raise RuntimeError(f"{fn.__name__}(mode {mode}) failed ({rc})")
+
     def bmax_pass8(self, qf: torch.Tensor, qmeta: torch.Tensor, nq: int, slot_end: int,
                    label_mask: int = 0) -> torch.Tensor:
         """The int8 threshold-sample pass over slots [0, slot_end): [tiles, nq] per-tile maxima of
         approx - B (-FLT_MAX for a tile without a live row that carries codes)."""
-        tiles = (slot_end + TILE - 1) // TILE
-        bmax = torch.empty(tiles, nq, dtype=torch.float32, device="cuda")
-        rc = self.L.spl_search_mma_pass8(self.arena.desc, qf.data_ptr(), qmeta.data_ptr(), nq, 0, slot_end,
-                                         label_mask, 0, None, bmax.data_ptr(), None, None, 0, MMA_GRID,
-                                         torch.cuda.current_stream().cuda_stream)
-        if rc != 0:
-            raise RuntimeError(f"spl_search_mma_pass8(bmax) failed ({rc})")
+        bmax = torch.empty((slot_end + TILE - 1) // TILE, nq, dtype=torch.float32, device="cuda")
+        self.mma_pass("int8", (qf, qmeta), nq, slot_end, 0, label_mask, bmax=bmax)
         return bmax
 
     def keys_of(self, idx: torch.Tensor) -> List[List[Optional[str]]]:

@@ -29,10 +29,11 @@ out = sys.argv[1]
 
 
 def short(n):
-    for k in ("k_search_mma8", "k_search_mma16", "k_rescore", "k_search_thr", "k_search_qprep8", "k_search_qprep"):
-        if k in n:
-            mode = "<1>" if "ILi1E" in n or "<1>" in n else "<0>" if "ILi0E" in n or "<0>" in n else ""
-            return k + mode
+    for k in ("k_search_side", "k_rescore", "k_search_thr", "k_search_qprep8", "k_search_qprep"):
+        if k in n:  # k_search_side<OpInt8 | OpBf16, MODE>
+            op = "<OpInt8" if "OpInt8" in n else "<OpBf16" if "OpBf16" in n else ""
+            mode = ", 1>" if "ELi1E" in n or ", 1>" in n else ", 0>" if "ELi0E" in n or ", 0>" in n else ""
+            return k + op + mode
     return None
 
 

@@ -23,43 +23,23 @@ def _pass_ms(vs, ar, q, copy, iters):
     """One candidate (emit) pass over the whole arena for the first 256 queries, alone: thresholds
     from the arm's own sample pass, best of `iters` by device events."""
     import torch
-    from libsplinter_amd.ops.search import MMA_GRID, MMA_Q, TILE
+    from libsplinter_amd.ops.search import DELTA, MMA_GRID, MMA_Q, TILE
     qq = q[:MMA_Q].contiguous()
     n, slots = qq.shape[0], ar.slots
-    st = torch.cuda.current_stream().cuda_stream
     sample = max(TILE, min(slots, max(TILE * 4096, slots // 16)) // TILE * TILE)
     bmax = torch.empty(sample // TILE, n, dtype=torch.float32, device="cuda")
     cnt = torch.zeros(n, MMA_GRID, dtype=torch.int32, device="cuda")
     cand = torch.empty(n * MMA_GRID * 64, dtype=torch.int32, device="cuda")
-    if copy == "int8":
-        qf, qmeta = vs.qprep8(qq)
-
-        def run(end, mode, thr):
-            return vs.L.spl_search_mma_pass8(ar.desc, qf.data_ptr(), qmeta.data_ptr(), n, 0, end, 0, mode,
-                                             thr.data_ptr() if thr is not None else None,
-                                             bmax.data_ptr() if mode == 0 else None, cnt.data_ptr(), cand.data_ptr(),
-                                             64, MMA_GRID, st)
-        margin = 0.0
-    else:
-        from libsplinter_amd.ops.search import DELTA
-        qb = torch.zeros(MMA_Q, 768, dtype=torch.bfloat16, device="cuda")
-        qb[:n] = (qq / qq.norm(dim=1, keepdim=True).clamp_min(1e-30)).to(torch.bfloat16)
-        qf = qb.view(MMA_Q // 16, 16, 24, 4, 8).permute(0, 2, 3, 1, 4).contiguous()
-
-        def run(end, mode, thr):
-            return vs.L.spl_search_mma_pass(ar.desc, qf.data_ptr(), n, 0, end, 0, mode,
-                                            thr.data_ptr() if thr is not None else None,
-                                            bmax.data_ptr() if mode == 0 else None, cnt.data_ptr(), cand.data_ptr(),
-                                            64, MMA_GRID, st)
-        margin = 2 * DELTA
-    assert run(sample, 0, None) == 0
-    thr = (bmax.topk(10, dim=0).values[-1] - margin).contiguous()
+    kind = "int8" if copy == "int8" else "bf16"
+    qop = vs.qprep8(qq) if kind == "int8" else (vs.qprep16(qq),)
+    vs.mma_pass(kind, qop, n, sample, 0, bmax=bmax)
+    thr = (bmax.topk(10, dim=0).values[-1] - (0.0 if kind == "int8" else 2 * DELTA)).contiguous()
     best = 1e9
     for _ in range(iters + 1):
         cnt.zero_()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        assert run(slots, 1, thr) == 0
+        vs.mma_pass(kind, qop, n, slots, 1, thr=thr, cnt=cnt, cand=cand, capb=64)
         e1.record()
         torch.cuda.synchronize()
         best = min(best, e0.elapsed_time(e1))

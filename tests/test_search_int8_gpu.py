@@ -1,5 +1,5 @@
 """The opt-in int8 candidate copy of an HBM arena (SPLINTER_HBM_VEC8=1; csrc/include/splinter_layout.hpp,
-csrc/hip/search_kernels.hip mf8): every vector writer keeps the int8 row and its rigorous per-row
+csrc/hip/search_kernels.hip side::OpInt8): every vector writer keeps the int8 row and its rigorous per-row
 error bound in step with the fp32 vector, the int8 MFMA pass computes exactly the integer dot
 products and the bound the layout defines, and the batched search on it returns the exact fp32
 kernel's result -- from Python, from the C ABI and from a node whose shards do not all carry the copy."""
