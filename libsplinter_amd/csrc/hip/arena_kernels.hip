@@ -210,15 +210,14 @@ __device__ __forceinline__ void dma16(const void* gsrc, uint32_t lds_base, bool 
                  : "memory");
 }
 
-// NR > 0: NR more row instructions per batch go through registers beside the NB staged ones
-// (4 (NB + NR) rows in flight).
-template <int NE, int MO = 0, bool LD1 = false, int NB = 6, int NR = 0>
+// (Measured and removed: 16 more rows per batch through registers beside the 24 staged ones, KV-only
+// 5.21-5.30 against 5.15-5.29 G ops/s, the same: profiles/r6/README.md.)
+template <int NE, int MO = 0, bool LD1 = false, int NB = 6>
 __device__ __forceinline__ void coop_copy_dma(const uint4* __restrict__ ep, const uint2* __restrict__ el, int lane,
                                               uint32_t rowb, uint4* stage) {
   const int q = lane >> 4, cl = lane & 15;
   const uint32_t sbase =
       __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)stage);
-  constexpr int NT = NB + NR;
   auto put = [&](int e, uint4 v, uint32_t c) {  // chunk c of entry e's row: masked, to its destination
     const uint2 L = el[e];
     if (c >= L.y) return;
@@ -233,7 +232,7 @@ __device__ __forceinline__ void coop_copy_dma(const uint4* __restrict__ ep, cons
     if (c * 16 + 16 > rowb) store_partial((uint8_t*)(dst + c), v, rowb - c * 16);
     else st16<MO>(dst + c, v);
   };
-  for (int e0 = 0; e0 < NE; e0 += 4 * NT) {
+  for (int e0 = 0; e0 < NE; e0 += 4 * NB) {
     // issue: row e0 + 4u + q, chunk cl of every instruction u; u < NB into stage[u KB + lane 16 B]
 #pragma unroll
     for (int u = 0; u < NB; ++u) {
@@ -244,33 +243,12 @@ __device__ __forceinline__ void coop_copy_dma(const uint4* __restrict__ ep, cons
       const uint4* src = (const uint4*)(((uint64_t)P.y << 32) | P.x);
       if ((uint32_t)cl < n16) dma16(src + cl, sbase + u * 1024, LD1);
     }
-    u32x4c_t t[NR > 0 ? NR : 1];
-#pragma unroll
-    for (int u = 0; u < NR; ++u) {
-      const int e = e0 + 4 * (NB + u) + q;
-      t[u] = u32x4c_t{0u, 0u, 0u, 0u};
-      if (e < NE) {
-        const uint4 P = ep[e];
-        const uint32_t n16 = (el[e].x + 15) >> 4;
-        const uint4* src = (const uint4*)(((uint64_t)P.y << 32) | P.x);
-        if ((uint32_t)cl < n16) t[u] = LD1 ? ld16c(src + cl) : __builtin_bit_cast(u32x4c_t, src[cl]);
-      }
-    }
-    // this wave's DMAs and register loads have landed
-    if constexpr (NR == 4)
-      asm volatile("s_waitcnt vmcnt(0)" : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3])::"memory");
-    else
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's DMAs have landed
 #pragma unroll
     for (int u = 0; u < NB; ++u) {
       const int e = e0 + 4 * u + q;
       if (e >= NE) break;
       put(e, stage[u * 64 + lane], (uint32_t)cl);
-    }
-#pragma unroll
-    for (int u = 0; u < NR; ++u) {
-      const int e = e0 + 4 * (NB + u) + q;
-      if (e < NE) put(e, make_uint4(t[u].x, t[u].y, t[u].z, t[u].w), (uint32_t)cl);
     }
     // the next batch's DMAs overwrite the stage: every ds_read of this one has returned
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");

@@ -19,8 +19,6 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdlib>
-#include <map>
-#include <mutex>
 #include <type_traits>
 
 #include "glds_asm.hpp"
@@ -43,7 +41,6 @@ __device__ __forceinline__ float bf2f(uint16_t h) { return __uint_as_float((uint
 // fp32 -> bf16, round-to-nearest-even, on the hardware converter (v_cvt_pk_bf16_f32: one
 // instruction per PAIR via pk2, instead of a 5-op integer rounding sequence per value)
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint16_t f2bf(float f) { return __builtin_bit_cast(uint16_t, (__bf16)f); }
 __device__ __forceinline__ uint32_t pk2(float a, float b) {
   const bf16x2_t v = {(__bf16)a, (__bf16)b};
   return __builtin_bit_cast(uint32_t, v);
@@ -51,7 +48,6 @@ __device__ __forceinline__ uint32_t pk2(float a, float b) {
 
 // Stage one BMxBK tile of a K-contiguous matrix (row stride ld elements)
 // starting at (row0, k0) into the lane-linear LDS image at `dst`.
-template <bool AS = false>
 __device__ __forceinline__ void stage_tile(const uint16_t* __restrict__ src, long ld, long row0, int k0,
                                            char* dst, int wave, int lane) {
 #pragma unroll
@@ -61,10 +57,7 @@ __device__ __forceinline__ void stage_tile(const uint16_t* __restrict__ src, lon
     const int pc = lane & 7;               // physical 16-B chunk in the 128-B row
     const int c = pc ^ (r & 7);            // logical chunk stored there
     const uint16_t* g = src + (row0 + r) * ld + k0 + c * 8;
-    if constexpr (AS)
-      spl::glds16_asm(g, dst + blk * 1024);  // counted LDS waits (glds_asm.hpp)
-    else
-      __builtin_amdgcn_global_load_lds((gbl_void*)g, (lds_void*)(dst + blk * 1024), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds((gbl_void*)g, (lds_void*)(dst + blk * 1024), 16, 0, 0);
   }
 }
 
@@ -146,7 +139,7 @@ __device__ __forceinline__ float swiglu(float up, float g) {
   return up * g * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-g * 1.4426950408889634f));
 }
 
-template <int MODE, bool AS = false>
+template <int MODE>
 __global__ __launch_bounds__(kThreads, 2) void k_gemm_nt(const uint16_t* __restrict__ A, long lda,
                                                          const uint16_t* __restrict__ W, long ldw, int K,
                                                          int mtiles, int ntiles, EpiArgs ep) {
@@ -197,8 +190,8 @@ __global__ __launch_bounds__(kThreads, 2) void k_gemm_nt(const uint16_t* __restr
     lb = *(const uint4*)(ep.lnb + n0 + c8);
   }
   // LDS: [A0 | B0 | A1 | B1], 16 KB each
-  stage_tile<AS>(A, lda, m0, 0, smem, wave, lane);
-  stage_tile<AS>(W, ldw, n0, 0, smem + kTileBytes, wave, lane);
+  stage_tile(A, lda, m0, 0, smem, wave, lane);
+  stage_tile(W, ldw, n0, 0, smem + kTileBytes, wave, lane);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   if constexpr (needs_rowstats(MODE)) {
     if (tid < 128) {  // Chan's combination of equal-size partials (as k_row_stats)
@@ -221,8 +214,8 @@ __global__ __launch_bounds__(kThreads, 2) void k_gemm_nt(const uint16_t* __restr
     const int cur = kt & 1;
     if (kt + 1 < nk) {
       char* nb = smem + (cur ^ 1) * 2 * kTileBytes;
-      stage_tile<AS>(A, lda, m0, (kt + 1) * BK, nb, wave, lane);
-      stage_tile<AS>(W, ldw, n0, (kt + 1) * BK, nb + kTileBytes, wave, lane);
+      stage_tile(A, lda, m0, (kt + 1) * BK, nb, wave, lane);
+      stage_tile(W, ldw, n0, (kt + 1) * BK, nb + kTileBytes, wave, lane);
     }
     const char* ta = smem + cur * 2 * kTileBytes;
     const char* tb = ta + kTileBytes;
@@ -437,9 +430,6 @@ static_assert(kLds2SplitBytes >= kLds2Bytes && kLds2SplitBytes <= 160 * 1024, "L
 
 __device__ __forceinline__ void wait_vm(int n) {
   switch (n) {  // wave-uniform: scalar branch to an immediate count
-    case 26: asm volatile("s_waitcnt vmcnt(26)" ::: "memory"); break;
-    case 20: asm volatile("s_waitcnt vmcnt(20)" ::: "memory"); break;
-    case 18: asm volatile("s_waitcnt vmcnt(18)" ::: "memory"); break;
     case 10: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
     case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
     case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
@@ -464,24 +454,12 @@ __device__ __forceinline__ uint4 pack8(const float* v) {
   return o;
 }
 
-// ILV > 0: each phase's two LDS-DMA instructions are issued between its MFMA groups (before the
-// groups u = ILV and ILV + 4 of the 8 (kk, i) groups of 2 MFMAs) instead of all before the first
-// MFMA -- a DMA instruction's ~100-cycle issue cost then overlaps the other wave's MFMAs on the
-// SIMD instead of holding both waves off the matrix core right after the barrier (the finding of
-// gemm_rln.hip's ILV variants).  The issue ORDER of the DMAs is unchanged, so the counted vmcnt
-// waits and the WAR/RAW distances of the phase schedule hold as they are.
-// EPI 1 (SWIGLU only): the SwiGLU is applied in registers -- with pack_upgate's [up16 | gate16]
-// column blocks, a lane's accumulators acc[..][j = 0] and acc[..][j = 1] are the up and gate values of
-// the same output -- and the bf16 results are paired across lanes (lane ^ 1, one DPP move) into
-// 4-B LDS writes of a 256 x 128 bf16 image, read back as 16-B row chunks: 32 ds_write_b32 per lane
-// instead of 128 fp32 ones, one barrier pair instead of two.
-// PP 1: ping-pong main loop (the guide's staggered 8-wave schedule, cdna_hip_programming.md §5 "The 256²
-// 8-phase template"): every phase is a LOAD section (its fragment ds_reads, one half-tile of LDS-DMA,
-// lgkmcnt(0)) and an MFMA section, each closed by a barrier, and waves 4-7 start one barrier behind
-// waves 0-3, so on every SIMD one wave's 16 MFMAs run beside its partner's loads.  Counted vmcnt(6)
-// once per K-tile (phase 4) retires the next K-tile; a half-tile is restaged one phase after its last
-// read, which is safe because each load section drains its reads before its closing barrier.
-template <int MODE, int ILV = 0, int EPI = 0, int PP = 0>
+// The LDS-DMAs are issued from inline asm (glds_asm.hpp): with the builtin, hipcc put lgkmcnt(0)
+// before every MFMA group of the loop.  Both K loops are peeled (the steady-state K-tiles carry no
+// staging branches) and issue their fragment reads in the order the MFMAs consume them (k-step
+// 0's B and A fragments first), pinned there, so the first MFMAs wait only for their own operands
+// (counted lgkmcnt) instead of the whole phase's reads.
+template <int MODE>
 __global__ __launch_bounds__(kThreads2, 1) void k_gemm256(const uint16_t* __restrict__ A, long lda,
                                                           const uint16_t* __restrict__ W, long ldw, int K,
                                                           int mtiles, int ntiles, EpiArgs ep) {
@@ -530,10 +508,7 @@ __global__ __launch_bounds__(kThreads2, 1) void k_gemm256(const uint16_t* __rest
     const uint16_t* base = (which < 2 ? A : W) + (long)t * BK;
     char* dst = smem + buf * kBufBytes + which * kHalfBytes;
     const uint32_t off = which == 0 ? offA[0][i] : which == 1 ? offA[1][i] : which == 2 ? offB[0][i] : offB[1][i];
-    if constexpr (PP == 2)
-      spl::glds16_asm(base + off, dst + (i * 8 + wave) * 1024);  // counted LDS waits (glds_asm.hpp)
-    else
-      __builtin_amdgcn_global_load_lds((gbl_void*)(base + off), (lds_void*)(dst + (i * 8 + wave) * 1024), 16, 0, 0);
+    spl::glds16_asm(base + off, dst + (i * 8 + wave) * 1024);  // counted LDS waits (glds_asm.hpp)
   };
   auto stage = [&](int which, int t, int buf) {
     stage_one(which, t, buf, 0);
@@ -557,6 +532,19 @@ __global__ __launch_bounds__(kThreads2, 1) void k_gemm256(const uint16_t* __rest
 
   const int nk = K / BK;
   bf16x8 af[4][2], b0[2][2], b1[2][2];
+  // one fragment read, pinned where it is written; one k-step of a quadrant's 8 MFMAs
+  auto rd = [](bf16x8& dst, const char* p) {
+    dst = *(const bf16x8*)p;
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  auto mm = [&](f32x4 (&ac)[4][2], bf16x8 (&bf)[2][2], int kk) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+        ac[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][kk], bf[j][kk], ac[i][j], 0, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);
+  };
   if (qh >= 0) {
     // ---- half-tile workgroup: rows qh*128 .. +127 of the tile, all 256 columns ----------------
     // LDS = ring of 3 stages x [A<qh> | B0 | B1] half-tiles (48 KB each, 144 KB).  K-tile t lives
@@ -577,24 +565,8 @@ __global__ __launch_bounds__(kThreads2, 1) void k_gemm256(const uint16_t* __rest
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         const uint32_t off = which == 0 ? oA[i] : which == 1 ? offB[0][i] : offB[1][i];
-        if constexpr (PP == 2)
-          spl::glds16_asm(base + off, dst + (i * 8 + wave) * 1024);
-        else
-          __builtin_amdgcn_global_load_lds((gbl_void*)(base + off), (lds_void*)(dst + (i * 8 + wave) * 1024), 16, 0,
-                                           0);
+        spl::glds16_asm(base + off, dst + (i * 8 + wave) * 1024);
       }
-    };
-    auto rd = [](bf16x8& dst, const char* p) {
-      dst = *(const bf16x8*)p;
-      __builtin_amdgcn_sched_barrier(0);
-    };
-    auto mm = [&](f32x4 (&ac)[4][2], bf16x8 (&bf)[2][2], int kk) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          ac[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][kk], bf[j][kk], ac[i][j], 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
     };
     hstage(0, 0, 0); hstage(1, 0, 0); hstage(2, 0, 0);
     if (nk > 1) { hstage(0, 1, 1); hstage(1, 1, 1); hstage(2, 1, 1); }
@@ -650,126 +622,6 @@ __global__ __launch_bounds__(kThreads2, 1) void k_gemm256(const uint16_t* __rest
   stage(0, 0, 0); stage(2, 0, 0); stage(3, 0, 0); stage(1, 0, 0);
   if (nk > 1) { stage(0, 1, 1); stage(2, 1, 1); stage(3, 1, 1); }
 
-  // one quadrant's 16 MFMAs (kk, i, j), with the phase's stage issued before them (ILV 0) or
-  // between the (kk, i) groups u = ILV and ILV + 4 (ILV > 0)
-  auto mma_phase = [&](f32x4 (&ac)[4][2], bf16x8 (&bf)[2][2], int which, int st, int sbuf, bool go) {
-    if (ILV == 0 && go) stage(which, st, sbuf);
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        if constexpr (ILV > 0) {
-          if (go && kk * 4 + i == ILV) stage_one(which, st, sbuf, 0);
-          if (go && kk * 4 + i == ILV + 4) stage_one(which, st, sbuf, 1);
-        }
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          ac[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][kk], bf[j][kk], ac[i][j], 0, 0, 0);
-        if constexpr (ILV > 0) __builtin_amdgcn_sched_barrier(0);
-      }
-    __builtin_amdgcn_s_setprio(0);
-  };
-  if constexpr (PP == 1) {
-    auto lgk0 = [] {
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_sched_barrier(0);
-    };
-    auto bar = [] {
-      __builtin_amdgcn_sched_barrier(0);
-      raw_barrier();
-      __builtin_amdgcn_sched_barrier(0);
-    };
-    auto mma_q = [&](f32x4 (&ac)[4][2], bf16x8 (&bf)[2][2]) {
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j)
-            ac[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][kk], bf[j][kk], ac[i][j], 0, 0, 0);
-      __builtin_amdgcn_s_setprio(0);
-    };
-    wait_vm(nk > 1 ? 6 : 0);  // K-tile 0 landed (K-tile 1's three half-tiles may still fly)
-    bar();
-    if (wr == 1) bar();  // the stagger
-    auto pp_kt = [&](int t, auto n1c, auto n2c) {
-      constexpr bool n1 = decltype(n1c)::value, n2 = decltype(n2c)::value;
-      const int buf = t & 1;
-      const char* hA0 = smem + buf * kBufBytes;
-      const char* hA1 = hA0 + kHalfBytes;
-      const char* hB0 = hA0 + 2 * kHalfBytes;
-      const char* hB1 = hA0 + 3 * kHalfBytes;
-      // phase 1: quadrant (0,0) -- read A0, B0; stage A1(t+1)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        b0[j][0] = *(const bf16x8*)(hB0 + (wn * 32 + j * 16) * 128 + frow + fsw0);
-        b0[j][1] = *(const bf16x8*)(hB0 + (wn * 32 + j * 16) * 128 + frow + fsw1);
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        af[i][0] = *(const bf16x8*)(hA0 + (wr * 64 + i * 16) * 128 + frow + fsw0);
-        af[i][1] = *(const bf16x8*)(hA0 + (wr * 64 + i * 16) * 128 + frow + fsw1);
-      }
-      if (n1) stage(1, t + 1, buf ^ 1);
-      lgk0();
-      bar();
-      mma_q(acc[0][0], b0);
-      bar();
-      // phase 2: quadrant (0,1) -- read B1; stage A0(t+2)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        b1[j][0] = *(const bf16x8*)(hB1 + (wn * 32 + j * 16) * 128 + frow + fsw0);
-        b1[j][1] = *(const bf16x8*)(hB1 + (wn * 32 + j * 16) * 128 + frow + fsw1);
-      }
-      if (n2) stage(0, t + 2, buf);
-      lgk0();
-      bar();
-      mma_q(acc[0][1], b1);
-      bar();
-      // phase 3: quadrant (1,0) -- read A1; stage B0(t+2)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        af[i][0] = *(const bf16x8*)(hA1 + (wr * 64 + i * 16) * 128 + frow + fsw0);
-        af[i][1] = *(const bf16x8*)(hA1 + (wr * 64 + i * 16) * 128 + frow + fsw1);
-      }
-      if (n2) stage(2, t + 2, buf);
-      lgk0();
-      bar();
-      mma_q(acc[1][0], b0);
-      bar();
-      // phase 4: quadrant (1,1) from registers; stage B1(t+2); retire K-tile t+1 (all but the 3 newest
-      // half-tiles, which belong to K-tile t+2)
-      if (n2) stage(3, t + 2, buf);
-      wait_vm(n2 ? 6 : 0);
-      bar();
-      mma_q(acc[1][1], b1);
-      bar();
-    };
-    // peeled: the steady-state K-tiles carry no staging branches (the counted waits and DMA issue are
-    // straight-line code the compiler can schedule around)
-    int t = 0;
-    for (; t + 2 < nk; ++t) pp_kt(t, std::true_type{}, std::true_type{});
-    if (t + 1 < nk) pp_kt(t++, std::true_type{}, std::false_type{});
-    if (t < nk) pp_kt(t, std::false_type{}, std::false_type{});
-    if (wr == 0) bar();  // equal barrier counts for both groups before the epilogue
-  } else if constexpr (PP == 2) {
-  // the lockstep loop below, peeled (no staging branches), with its fragment reads issued in the order
-  // the MFMAs consume them (k-step 0's B and A fragments first) and pinned there, so the first MFMAs wait
-  // only for their own operands (counted lgkmcnt) instead of the whole phase's reads
-  auto rd = [](bf16x8& dst, const char* p) {
-    dst = *(const bf16x8*)p;
-    __builtin_amdgcn_sched_barrier(0);
-  };
-  auto mm = [&](f32x4 (&ac)[4][2], bf16x8 (&bf)[2][2], int kk) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-        ac[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][kk], bf[j][kk], ac[i][j], 0, 0, 0);
-    __builtin_amdgcn_sched_barrier(0);
-  };
   auto ls_kt = [&](int t, auto n1c, auto n2c) {
     constexpr bool n1 = decltype(n1c)::value, n2 = decltype(n2c)::value;
     const int buf = t & 1;
@@ -843,88 +695,8 @@ __global__ __launch_bounds__(kThreads2, 1) void k_gemm256(const uint16_t* __rest
   for (; t + 2 < nk; ++t) ls_kt(t, std::true_type{}, std::true_type{});
   if (t + 1 < nk) ls_kt(t++, std::true_type{}, std::false_type{});
   if (t < nk) ls_kt(t, std::false_type{}, std::false_type{});
-  } else
-  for (int t = 0; t < nk; ++t) {
-    const int buf = t & 1;
-    const char* hA0 = smem + buf * kBufBytes;
-    const char* hA1 = hA0 + kHalfBytes;
-    const char* hB0 = hA0 + 2 * kHalfBytes;
-    const char* hB1 = hA0 + 3 * kHalfBytes;
-    const bool n1 = t + 1 < nk, n2 = t + 2 < nk;
-    // ---- phase 1: quadrant (0,0)
-    wait_vm(n1 ? 10 : 4);
-    raw_barrier();
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      b0[j][0] = *(const bf16x8*)(hB0 + (wn * 32 + j * 16) * 128 + frow + fsw0);
-      b0[j][1] = *(const bf16x8*)(hB0 + (wn * 32 + j * 16) * 128 + frow + fsw1);
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      af[i][0] = *(const bf16x8*)(hA0 + (wr * 64 + i * 16) * 128 + frow + fsw0);
-      af[i][1] = *(const bf16x8*)(hA0 + (wr * 64 + i * 16) * 128 + frow + fsw1);
-    }
-    mma_phase(acc[0][0], b0, 1, t + 1, buf ^ 1, n1);
-    // ---- phase 2: quadrant (0,1)
-    wait_vm(n1 ? 10 : 2);
-    raw_barrier();
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      b1[j][0] = *(const bf16x8*)(hB1 + (wn * 32 + j * 16) * 128 + frow + fsw0);
-      b1[j][1] = *(const bf16x8*)(hB1 + (wn * 32 + j * 16) * 128 + frow + fsw1);
-    }
-    mma_phase(acc[0][1], b1, 0, t + 2, buf, n2);
-    // ---- phase 3: quadrant (1,0)
-    wait_vm(n2 ? 10 : (n1 ? 8 : 0));
-    raw_barrier();
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      af[i][0] = *(const bf16x8*)(hA1 + (wr * 64 + i * 16) * 128 + frow + fsw0);
-      af[i][1] = *(const bf16x8*)(hA1 + (wr * 64 + i * 16) * 128 + frow + fsw1);
-    }
-    mma_phase(acc[1][0], b0, 2, t + 2, buf, n2);
-    // ---- phase 4: quadrant (1,1), registers only (B1's last read was phase 2: a barrier ago)
-    mma_phase(acc[1][1], b1, 3, t + 2, buf, n2);
-  }
   }  // whole tile
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-
-  if constexpr (MODE == NOMIC_EPI_SWIGLU && EPI == 1) {  // (whole tiles only: never launched with a tail split)
-    constexpr int kS = 128 + 8;  // bf16 row stride of the image (272 B: conflict-free 4-B writes)
-    uint16_t* E16 = (uint16_t*)smem;
-    const int fq = lane >> 4, fr = lane & 15;
-    const bool odd = fr & 1;
-    __syncthreads();  // every wave is done reading the last K-tile's operands
-#pragma unroll
-    for (int qm = 0; qm < 2; ++qm)
-#pragma unroll
-      for (int qn = 0; qn < 2; ++qn)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          uint32_t b[4];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) b[r] = f2bf(swiglu(acc[qm][qn][i][0][r], acc[qm][qn][i][1][r]));
-          // even lanes write rows r = 0, 1 at columns (fr, fr + 1), odd lanes rows 2, 3 at (fr - 1, fr)
-          const uint32_t send = odd ? (b[0] | b[1] << 16) : (b[2] | b[3] << 16);
-          const uint32_t recv = (uint32_t)__builtin_amdgcn_mov_dpp((int)send, 0xB1, 0xf, 0xf, false);
-          const uint32_t w0 = odd ? ((recv & 0xffffu) | b[2] << 16) : (b[0] | recv << 16);
-          const uint32_t w1 = odd ? ((recv >> 16) | b[3] << 16) : (b[1] | (recv & 0xffff0000u));
-          const int row = qm * 128 + wr * 64 + i * 16 + fq * 4 + (odd ? 2 : 0);
-          const int col = (qn * 4 + wn) * 16 + (fr & ~1);
-          *(uint32_t*)(E16 + row * kS + col) = w0;
-          *(uint32_t*)(E16 + (row + 1) * kS + col) = w1;
-        }
-    __syncthreads();
-#pragma unroll
-    for (int it = 0; it < (256 * 16) / kThreads2; ++it) {
-      const int q = tid + it * kThreads2;
-      const int row = q >> 4, c = q & 15;
-      const long gm = m0 + row;
-      if (gm >= ep.M) continue;
-      *(uint4*)(ep.out + gm * ep.ldo + (long)nt * 128 + c * 8) = *(const uint4*)(E16 + row * kS + c * 8);
-    }
-    return;
-  }
 
   // ---- epilogue: two 128-row halves through the fp32 LDS image ------------
   // (a half-tile block holds its one half in acc[0] and runs the first pass only, on rows of qh)
@@ -1066,11 +838,24 @@ void allow_lds(F* f, int bytes) {
   (void)hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
 }
 
-// Kernel choice (NOMIC_GEMM): 0 = auto, 128 = the 128^2 kernel, 256 = the 256^2 kernel.  The
-// persistent / stream-K 256^2 kernel (512-515), the DMA-interleave (ILV), ping-pong (PP), asm-DMA
-// 128^2 (AS128), register-SwiGLU-epilogue and persistent register-epilogue (300, gemm_pt.hip, round
-// 5) knobs measured slower or equal and are gone; their A/B history is in profiles/r1_gemm_*.jsonl
-// .. r3_gemm_*, r5/gemm_pt_ab_r5c.jsonl.
+// Kernel choice (NOMIC_GEMM): 0 = auto, 128 = the 128^2 kernel, 256 = the 256^2 kernel.
+//
+// Measured and removed (SwiGLU shape, M = 32768, unless said otherwise):
+//   - persistent / stream-K 256^2 kernel (512-515) and the persistent register-epilogue kernel
+//     (300, gemm_pt.hip, round 5): slower or equal (profiles/r1_gemm_persistent_ab.jsonl,
+//     r2_gemm_streamk_ab.jsonl, r5/gemm_pt_ab_r5c.jsonl)
+//   - the lockstep K loop with builtin LDS-DMA and all of a phase's reads before its MFMAs (PP 0):
+//     296.5 us against 285.2 for the peeled asm-DMA loop that stayed, qkv 146.9 against 137.4
+//     (profiles/r3_gemm_asm_dma.md, r3_gemm_pp2_ab.jsonl)
+//   - the staggered ping-pong loop (PP 1: waves 4-7 one barrier behind, a load and an MFMA section
+//     per phase): 310.2 against 314.2 us, +1 %, issue stalls turned into barrier waits
+//     (profiles/r3_gemm_pp_ab.jsonl)
+//   - a phase's two DMAs issued between its MFMA groups (ILV 1-3): -1 % on this kernel, +3 % on the
+//     persistent one (profiles/r3_gemm_ilv_ab.jsonl)
+//   - SwiGLU applied in registers with a lane-paired bf16 LDS image (EPI 1): 295.7 us, neutral,
+//     the epilogue is not the limiter (profiles/r3_gemm_asm_dma.md)
+//   - asm DMA in the 128^2 kernel (AS128): 144 against 140 us on the qkv shape
+//     (profiles/r3_gemm_asm_dma.md, r3_gemm_asm_dma_rln_128_ab.jsonl)
 int g_variant = -1;
 int gemm_variant() {
   if (g_variant < 0) {
@@ -1114,7 +899,7 @@ int launch(const uint16_t* A, long lda, const uint16_t* W, long ldw, long M, int
   }();
   if (k256_ok && fits && (var == 256 || (var == 0 && tiles256 >= min_tiles))) {
     static bool attr = [] {
-      allow_lds(k_gemm256<MODE, 0, 0, 2>, kLds2SplitBytes);
+      allow_lds(k_gemm256<MODE>, kLds2SplitBytes);
       return true;
     }();
     (void)attr;
@@ -1123,7 +908,7 @@ int launch(const uint16_t* A, long lda, const uint16_t* W, long ldw, long M, int
     ep.nsplit = split_tiles(tiles256);
     // a launch without half-tile blocks is what it was: same grid, same LDS size
     if constexpr (k256_ok)
-      hipLaunchKernelGGL((k_gemm256<MODE, 0, 0, 2>), dim3(mtiles * ntiles + ep.nsplit), dim3(kThreads2),
+      hipLaunchKernelGGL((k_gemm256<MODE>), dim3(mtiles * ntiles + ep.nsplit), dim3(kThreads2),
                          ep.nsplit ? kLds2SplitBytes : kLds2Bytes, s, A, lda, W, ldw, K, mtiles, ntiles, ep);
     return (int)hipGetLastError();
   }

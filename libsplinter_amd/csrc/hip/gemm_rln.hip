@@ -16,9 +16,10 @@
 // residual loads, LayerNorm and the bf16 stores work on 8-byte row pieces straight from registers
 // (16-byte pieces in the default form, after lanes l and l ^ 16 exchange halves: EPI 4 below).
 //
-// K loop: BK = 32 (one MFMA k-step), two LDS buffers of [A 128 x 32 | W 768 x 32] bf16 (56 KB
-// each), filled by global_load_lds_dwordx4 (LDS-DMA; 7 wave-instructions per wave per stage) one
-// stage ahead of the MFMAs, counted vmcnt + raw s_barrier (no vmcnt(0) drain in the loop).  The
+// K loop: BK = 32 (one MFMA k-step), LDS rings of three W stages (768 x 32 bf16, 48 KB each) and
+// two A stages (128 x 32, 8 KB each), filled by global_load_lds_dwordx4 (LDS-DMA; 7
+// wave-instructions per wave per stage) two and one stages ahead of the MFMAs and issued between
+// them, counted vmcnt + raw s_barrier (no vmcnt(0) drain in the loop).  The
 // LDS image has 64-byte rows; the 16-byte chunk c of row r is stored at chunk c ^ ((r >> 1) & 3),
 // which makes every ds_read_b128 lane group (16 lanes) hit 16 distinct bank slots (brute-forced
 // over the gfx950 b128 lane groups); glds writes lane-linearly, so the XOR is applied to the
@@ -31,7 +32,6 @@
 #include <cstdint>
 #include <cstdlib>
 
-#include "glds_asm.hpp"
 #include "nomic_api.h"
 
 namespace {
@@ -51,27 +51,15 @@ constexpr int kThreads = 512;
 constexpr int kRowBytes = kBK * 2;                   // 64
 constexpr int kABytes = kBM * kRowBytes;             // 8 KB per A stage
 constexpr int kWBytes = kN * kRowBytes;              // 48 KB per W stage
-constexpr int kGldsW = kWBytes / 1024 / 8;           // W wave-instructions per wave per stage (6)
 constexpr int kEpiLds = 4 * kBM * 4;                 // epilogue: [4 column waves][128 rows] fp32 row sums
 
-// K pipelines (template PIPE): LDS rings of NW W-stages and NA A-stages, one barrier per stage.
-// Iteration t, after its barrier, issues the stages W(t + NW - 1) and A(t + NA - 1) (the one with
-// the shorter lead first) into ring slots last read in iteration t-1, then computes stage t.
-//   PIPE 1: NW 2, NA 4 (128 KB): A -- streamed from HBM, read once -- three stages ahead
-//   PIPE 2: NW 3, NA 2 (160 KB): W -- L2-resident, re-read by every workgroup -- two stages ahead
-//   PIPE 3: NW 2, NA 2 (112 KB): both one stage ahead
-template <int PIPE> struct Pipe;
-template <> struct Pipe<1> { static constexpr int NW = 2, NA = 4; };
-template <> struct Pipe<2> { static constexpr int NW = 3, NA = 2; };
-template <> struct Pipe<3> { static constexpr int NW = 2, NA = 2; };
-//   PIPE 4: NW 2, NA 6 (144 KB): A five stages ahead
-template <> struct Pipe<4> { static constexpr int NW = 2, NA = 6; };
-template <int PIPE>
-constexpr int lds_bytes() {
-  return Pipe<PIPE>::NW * kWBytes + Pipe<PIPE>::NA * kABytes > kEpiLds
-             ? Pipe<PIPE>::NW * kWBytes + Pipe<PIPE>::NA * kABytes
-             : kEpiLds;
-}
+// K pipeline: LDS rings of kNW W stages and kNA A stages, one barrier per stage.  Iteration t,
+// after its barrier, issues the stages A(t + kNA - 1) and W(t + kNW - 1) into ring slots last read
+// in iteration t-1, then computes stage t: W -- L2-resident, re-read by every workgroup -- runs two
+// stages ahead, A -- streamed from HBM, read once -- one.
+constexpr int kNW = 3, kNA = 2;
+constexpr int kLdsBytes = kNW * kWBytes + kNA * kABytes;  // 160 KB: [W ring | A ring]
+static_assert(kLdsBytes <= 160 * 1024 && kLdsBytes >= kEpiLds, "LDS budget");
 
 __device__ __forceinline__ float bf2f(uint32_t h16) { return __uint_as_float(h16 << 16); }
 __device__ __forceinline__ uint32_t pk2(float a, float b) {
@@ -87,10 +75,7 @@ __device__ __forceinline__ void raw_barrier() {
 
 __device__ __forceinline__ void wait_vm(int n) {
   switch (n) {  // wave-uniform: a scalar branch to an immediate count
-    case 12: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
     case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-    case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-    case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
     default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
   }
 }
@@ -102,52 +87,55 @@ __device__ __forceinline__ uint32_t xor16(uint32_t v) { return (uint32_t)__built
 // physical 16-B chunk of logical chunk c in 64-B row r
 __device__ __forceinline__ int swz(int r, int c) { return c ^ ((r >> 1) & 3); }
 
-// WM: waves along M.  2: 8 waves (2 x 4), 64 rows x 192 columns each (192 accumulators, two
-// waves per SIMD).  1: 4 waves (1 x 4), 128 rows x 192 columns each (384 accumulators in the
-// AGPR half of a 512-register wave, one wave per SIMD, 8 A fragments per stage: a third less
-// LDS read traffic per MFMA and half the waves at each barrier).
-// ILV > 0: the loads an iteration issues are spread over its MFMA groups (ILV LDS-DMA
-// instructions ahead of each group of 8 MFMAs, in issue order) instead of all issued after the
-// barrier, where they held both waves of a SIMD off the matrix core for the ~100-cycle issue cost
-// of each DMA instruction.  ILV 0: all after the barrier.
-// EPI 0: residual added in the epilogue (8-B loads); 2: the residual is
-// the first K step -- one MFMA per tile against an identity operand (acc = I . R, exact: 1.0 x a
-// bf16 value) with R fragments loaded in the prologue beside the first stages, so the epilogue
-// reads nothing.  3 (K = 768, the o-proj): the residual is added during the K loop -- stage t
-// loads the lane's residual pieces of two of its 48 (m-tile, n-tile) accumulator tiles, stage t + 1
-// adds them -- so the epilogue only normalises and stores: the residual's 50 MB at M = 32768 no
-// longer arrive while every workgroup sits in its epilogue (o-proj 62.6 -> 56.3 us; the down
-// projection, K = 3072, gains nothing from it: 146.3 vs 147.1 us, profiles/r4aq).  4: EPI 0 with
-// 16-B residual loads and output stores from registers (24 of each per lane instead of 48 8-B
-// ones; lane pairs l, l ^ 16 exchange halves, see the epilogue): o-proj 64.0 -> 51.4 us, down
-// 149.8 -> 138.0 us, the same bits (profiles/encoder_tails).  It needs 16-B aligned residual and
-// output rows; the entry point runs EPI 0 where they are not.  (16-B stores on EPI 3 measured 57.9
-// us on the o-proj, no better than EPI 3 itself; an LDS-staged 16-B epilogue spilled 109 registers
-// into the K loop and took 420 us on the down shape: both are gone.)
-// PF: W fragment pairs read PF pairs ahead of their MFMAs.
-// AS: the K-loop's LDS-DMAs issued from inline asm (glds_asm.hpp: counted lgkmcnt before the MFMAs)
-// ROT: block b walks the K steps starting at step b mod nk (the sum is order-free up to fp32 rounding), so
-// the 256 blocks that start together fetch different W stages instead of all hitting the same L2 lines
-template <int PIPE, int EPI, int WM, int ILV = 0, int PF = 1, bool AS = false, bool ROT = false>
-__global__ __launch_bounds__(256 * WM, 1) void k_gemm_rln(const uint16_t* __restrict__ A, long lda,
+// EPI 0: residual added in the epilogue (8-B loads).  3 (K = 768, the o-proj): the residual is
+// added during the K loop -- stage t loads the lane's residual pieces of two of its 48 (m-tile,
+// n-tile) accumulator tiles, stage t + 1 adds them -- so the epilogue only normalises and stores:
+// the residual's 50 MB at M = 32768 no longer arrive while every workgroup sits in its epilogue
+// (o-proj 62.6 -> 56.3 us; the down projection, K = 3072, gains nothing from it: 146.3 vs 147.1 us,
+// profiles/r4aq).  4: EPI 0 with 16-B residual loads and output stores from registers (24 of each
+// per lane instead of 48 8-B ones; lane pairs l, l ^ 16 exchange halves, see the epilogue): o-proj
+// 64.0 -> 51.4 us, down 149.8 -> 138.0 us, the same bits (profiles/encoder_tails).  It needs 16-B
+// aligned residual and output rows; the entry point runs EPI 0 where they are not.
+//
+// Measured and removed (each was a template parameter of this kernel; o-proj / down at M = 32768;
+// variant numbers are round 3's -- 2, ring, DMAs per MFMA pair -- not today's NOMIC_RLN values):
+//   - all of a stage's DMAs issued right after the barrier (ILV 0, variant 220): 67.6 / 152.0 us
+//     against 59.1 / 144.7 with two DMAs ahead of each MFMA pair (222); three per pair (ILV 3, on
+//     the PIPE 1 and 4 rings: 213, 243): 66.2 / 156.4 and 66.7 / 157.2 (profiles/r3_rln_ab.jsonl)
+//   - rings of 2 W + 4 A stages and 2 W + 6 A stages (PIPE 1, 4: variants 212, 242 of that file):
+//     59.7 / 146.4 and 60.2 / 147.7 against 59.1 / 144.7; 2 W + 2 A (PIPE 3): the first form,
+//     from before the A/B files
+//   - the residual as the first K step, an MFMA against an identity operand (EPI 2), and W
+//     fragments read two pairs ahead (PF 2): within +-1 % or slower (profiles/r3_pmc_encoder.md,
+//     r3_rln_variants_ab.jsonl)
+//   - the K loop's DMAs from inline asm (AS): o-proj 61.4 against 62.6, down 150.1 against 147.1,
+//     embed step 9.28-9.34 against 9.20 ms (profiles/r3_gemm_asm_dma.md)
+//   - block b starting its K walk at step b mod nk (ROT): equal at K 128 / 768, +7 % at K 3072
+//     (profiles/r3_rln_rot_ab.jsonl)
+//   - 4 waves of 128 rows x 192 columns (WM 1): built for the A/B harness, no measurement kept
+//   - 16-B stores on EPI 3: o-proj 57.9 us, no better than EPI 3 itself; an LDS-staged 16-B
+//     epilogue: 109 registers spilled into the K loop, 420 us on the down shape
+//     (profiles/encoder_tails/rln_ab.jsonl)
+template <int EPI>
+__global__ __launch_bounds__(kThreads, 1) void k_gemm_rln(const uint16_t* __restrict__ A, long lda,
                                                           const uint16_t* __restrict__ W, long ldw, int K, long M,
                                                           const uint16_t* res, long ldr,
                                                           const uint16_t* __restrict__ gamma,
                                                           const uint16_t* __restrict__ beta, float eps,
                                                           uint16_t* out, long ldo) {
-  constexpr int NW = Pipe<PIPE>::NW, NA = Pipe<PIPE>::NA;
-  constexpr int LW = NW - 1, LA = NA - 1;              // stages of lead
-  constexpr int kABase = NW * kWBytes;                 // LDS: [W ring | A ring]
-  constexpr int kWaves = 4 * WM, kNThreads = 64 * kWaves;
-  constexpr int RW = kBM / WM, MT = RW / 16;           // rows and m-tiles per wave
+  constexpr int LW = kNW - 1, LA = kNA - 1;            // stages of lead
+  static_assert(LW > LA, "an iteration issues its A stage before its W stage");
+  constexpr int kABase = kNW * kWBytes;                // LDS: [W ring | A ring]
+  constexpr int kWaves = kThreads / 64;                // 8 waves: 2 (rows) x 4 (columns)
+  constexpr int RW = kBM / 2, MT = RW / 16;            // rows and m-tiles per wave
   constexpr int GA = 8 / kWaves, GW = 48 / kWaves;     // LDS-DMA wave-instructions per wave per stage
   constexpr bool KRES = EPI == 3;  // residual added during the K loop
   constexpr bool WIDE = EPI == 4;  // 16-B epilogue I/O from registers
-  static_assert(EPI == 0 || EPI == 2 || EPI == 3 || EPI == 4, "epilogue forms");
+  static_assert(EPI == 0 || EPI == 3 || EPI == 4, "epilogue forms");
   static_assert(!KRES || MT * kNT == 48, "EPI 3 spreads 48 accumulator tiles over 24 stages");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wr = WM == 2 ? wave >> 2 : 0, wn = wave & 3;
+  const int wr = wave >> 2, wn = wave & 3;
   // W is read by every block and A rows by one block only: no reuse for an XCD remap to exploit
   const long m0 = (long)blockIdx.x * kBM;
 
@@ -167,53 +155,31 @@ __global__ __launch_bounds__(256 * WM, 1) void k_gemm_rln(const uint16_t* __rest
     offW[i] = (uint32_t)(r * ldw + swz(r, dpc) * 8);
   }
   const int nk = K / kBK;
-  // ring slot of stage t: t % NW (W), t % NA (A) -- stages enter each ring in order
-  const int rot = ROT ? (int)(blockIdx.x % (unsigned)nk) : 0;
-  auto kcol = [&](int t) -> long {  // global K offset of stage t
-    if constexpr (ROT) {
-      const int k = t + rot;
-      return (long)(k < nk ? k : k - nk) * kBK;
-    }
-    return (long)t * kBK;
-  };
+  // ring slot of stage t: t % kNW (W), t % kNA (A) -- stages enter each ring in order
   auto glds_w = [&](int t, int i) {
-    if constexpr (AS)
-      spl::glds16_asm(W + kcol(t) + offW[i], smem + (t % NW) * kWBytes + (wave + kWaves * i) * 1024);
-    else
-      __builtin_amdgcn_global_load_lds((gbl_void*)(W + kcol(t) + offW[i]),
-                                       (lds_void*)(smem + (t % NW) * kWBytes + (wave + kWaves * i) * 1024), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds((gbl_void*)(W + (long)t * kBK + offW[i]),
+                                     (lds_void*)(smem + (t % kNW) * kWBytes + (wave + kWaves * i) * 1024), 16, 0, 0);
   };
   auto glds_a = [&](int t, int i) {
-    if constexpr (AS)
-      spl::glds16_asm(A + kcol(t) + offA[i], smem + kABase + (t % NA) * kABytes + (wave + kWaves * i) * 1024);
-    else
-      __builtin_amdgcn_global_load_lds((gbl_void*)(A + kcol(t) + offA[i]),
-                                       (lds_void*)(smem + kABase + (t % NA) * kABytes + (wave + kWaves * i) * 1024),
-                                       16, 0, 0);
+    __builtin_amdgcn_global_load_lds((gbl_void*)(A + (long)t * kBK + offA[i]),
+                                     (lds_void*)(smem + kABase + (t % kNA) * kABytes + (wave + kWaves * i) * 1024),
+                                     16, 0, 0);
   };
-  // op u (0 .. GW+GA-1) of the loads iteration s issues: stage W(s + LW) and A(s + LA), the one
-  // with the shorter lead first (younger() counts on that order)
-  constexpr int kOps = GW + GA;
+  // op u (0 .. GA+GW-1) of the loads iteration s issues: stage A(s + LA), then W(s + LW) (the
+  // counted wait at the top of an iteration relies on that order)
+  constexpr int kOps = GA + GW;
+  static_assert(kOps <= kNT, "two DMAs ahead of each of the kNT / 2 MFMA pairs cover a stage's loads");
   auto issue_op = [&](int s, int u) {
     const int tw = s + LW, ta = s + LA;
-    if (LW <= LA) {
-      if (u < GW) { if (tw >= 0 && tw < nk) glds_w(tw, u); }
-      else if (ta >= 0 && ta < nk) glds_a(ta, u - GW);
-    } else {
-      if (u < GA) { if (ta >= 0 && ta < nk) glds_a(ta, u); }
-      else if (tw >= 0 && tw < nk) glds_w(tw, u - GA);
-    }
+    if (u < GA) { if (ta >= 0 && ta < nk) glds_a(ta, u); }
+    else if (tw >= 0 && tw < nk) glds_w(tw, u - GA);
   };
   auto issue = [&](int s) {
 #pragma unroll
     for (int u = 0; u < kOps; ++u) issue_op(s, u);
   };
-  // ops issued after the later of W(t) / A(t): they may stay in flight at the top of iteration t
-  auto younger = [&](int t) -> int {
-    if (LW < LA) return t + LA - 1 < nk ? GA : 0;           // A(t + LA - 1), issued after W(t)
-    if (LW > LA) return t + LW - 1 < nk ? GW : 0;           // W(t + LW - 1), issued after A(t)
-    return 0;
-  };
+  // W(t + LW - 1) was issued after A(t): it may stay in flight at the top of iteration t
+  auto younger = [&](int t) -> int { return t + LW - 1 < nk ? GW : 0; };
 
   // fragment read: row = base16 + (lane & 15), logical chunk lane >> 4
   const int fl = (lane & 15) * kRowBytes + (swz(lane & 15, lane >> 4) << 4);
@@ -221,38 +187,11 @@ __global__ __launch_bounds__(256 * WM, 1) void k_gemm_rln(const uint16_t* __rest
   const int woff = (wn * kWN) * kRowBytes + fl;
 
   f32x4 acc[MT][kNT];
-  constexpr int L = LW > LA ? LW : LA;
-  if constexpr (EPI == 2) {
-    // residual fragments (B operand of a 16x16x32 MFMA: lane l holds k = 8 (l >> 4) .. +7 of column
-    // l & 15): lanes 0-31 load res[m][n0 + 8 (l >> 4) .. +8] (16 B), lanes 32-63 (k 16-31) zero;
-    // identity A operand: row n = l & 15 has its 1 at k = n
-    bf16x8 rf[MT][kNT];
-    const int rl = lane & 15;
 #pragma unroll
-    for (int i = 0; i < MT; ++i) {
-      const long m = m0 + wr * RW + i * 16 + rl;
-      const uint16_t* rp = res + (m < M ? m : M - 1) * ldr + wn * kWN + 8 * ((lane >> 4) & 1);
+  for (int i = 0; i < MT; ++i)
 #pragma unroll
-      for (int j = 0; j < kNT; ++j) {
-        if (lane < 32) rf[i][j] = *(const bf16x8*)(rp + j * 16);
-        else rf[i][j] = bf16x8{};
-      }
-    }
-    for (int s = -L; s < 0; ++s) issue(s);
-    bf16x8 eye = bf16x8{};
-    if (lane < 32 && (rl >> 3) == (lane >> 4)) eye[rl & 7] = (__bf16)1.0f;
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-      for (int j = 0; j < kNT; ++j)
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(eye, rf[i][j], f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-  } else {
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-      for (int j = 0; j < kNT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int s = -L; s < 0; ++s) issue(s);
-  }
+    for (int j = 0; j < kNT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int s = -LW; s < 0; ++s) issue(s);
   // EPI 3: residual pieces of accumulator tile u = (u / kNT, u % kNT), two tiles per stage
   const long rmb = m0 + wr * RW + (lane & 15);
   const int rcq = (lane >> 4) * 4;
@@ -287,34 +226,27 @@ __global__ __launch_bounds__(256 * WM, 1) void k_gemm_rln(const uint16_t* __rest
         }
       }
     }
-    if (ILV == 0) issue(t);
-    const char* bw = smem + (t % NW) * kWBytes;
-    const char* ba = smem + (t % NA) * kABytes;
+    const char* bw = smem + (t % kNW) * kWBytes;
+    const char* ba = smem + (t % kNA) * kABytes;
     // A fragments for the whole stage, W fragments two n-tiles at a time with the next pair's reads
     // issued ahead of the current pair's MFMAs (sched_barrier pins the pairs: hoisting all 12 W
-    // reads would need 48 more registers than the 256 two waves per SIMD allow)
-    bf16x8 af[MT], w0, w1, x0, x1, y0, y1;
+    // reads would need 48 more registers than the 256 two waves per SIMD allow).  The stage's seven
+    // DMAs go two ahead of each MFMA pair, in issue order: issued together after the barrier they
+    // held both waves of a SIMD off the matrix core for the ~100-cycle issue cost of each.
+    bf16x8 af[MT], w0, w1, x0, x1;
 #pragma unroll
     for (int i = 0; i < MT; ++i) af[i] = *(const bf16x8*)(ba + aoff + i * 16 * kRowBytes);
     w0 = *(const bf16x8*)(bw + woff);
     w1 = *(const bf16x8*)(bw + woff + 16 * kRowBytes);
-    if (PF == 2) {
-      x0 = *(const bf16x8*)(bw + woff + 2 * 16 * kRowBytes);
-      x1 = *(const bf16x8*)(bw + woff + 3 * 16 * kRowBytes);
-    }
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int jp = 0; jp < kNT / 2; ++jp) {
-      if (ILV > 0) {
 #pragma unroll
-        for (int u = jp * ILV; u < (jp + 1) * ILV; ++u)
-          if (u < kOps) issue_op(t, u);
-      }
-      if (jp + PF < kNT / 2) {
-        bf16x8& d0 = PF == 2 ? y0 : x0;
-        bf16x8& d1 = PF == 2 ? y1 : x1;
-        d0 = *(const bf16x8*)(bw + woff + (2 * (jp + PF)) * 16 * kRowBytes);
-        d1 = *(const bf16x8*)(bw + woff + (2 * (jp + PF) + 1) * 16 * kRowBytes);
+      for (int u = 2 * jp; u < 2 * jp + 2; ++u)
+        if (u < kOps) issue_op(t, u);
+      if (jp + 1 < kNT / 2) {
+        x0 = *(const bf16x8*)(bw + woff + (2 * (jp + 1)) * 16 * kRowBytes);
+        x1 = *(const bf16x8*)(bw + woff + (2 * (jp + 1) + 1) * 16 * kRowBytes);
       }
 #pragma unroll
       for (int i = 0; i < MT; ++i) {
@@ -324,16 +256,8 @@ __global__ __launch_bounds__(256 * WM, 1) void k_gemm_rln(const uint16_t* __rest
       __builtin_amdgcn_sched_barrier(0);
       w0 = x0;
       w1 = x1;
-      if (PF == 2) {
-        x0 = y0;
-        x1 = y1;
-      }
     }
     __builtin_amdgcn_s_setprio(0);
-    if (ILV > 0) {
-#pragma unroll
-      for (int u = (kNT / 2) * ILV; u < kOps; ++u) issue_op(t, u);
-    }
   }
   if constexpr (KRES) {  // the last pair (loaded at stage 23)
     res_add(46, rq[0]);
@@ -346,8 +270,8 @@ __global__ __launch_bounds__(256 * WM, 1) void k_gemm_rln(const uint16_t* __rest
   // lane: rows m_i = m0 + wr*64 + i*16 + (lane & 15); columns n_j = wn*192 + j*16 + (lane>>4)*4 + 0..3
   const int rl = lane & 15, cq = (lane >> 4) * 4;
   {
-    // residual loads (EPI 0 / 4; EPI 2 and 3 have it in the accumulators) and stores from
-    // registers, in 8-B (EPI 0, 2, 3) or 16-B (EPI 4) row pieces
+    // residual loads (EPI 0 / 4; EPI 3 has it in the accumulators) and stores from registers, in
+    // 8-B (EPI 0, 3) or 16-B (EPI 4) row pieces
     float* red = (float*)smem;  // [4 column waves][128 rows]
     const long mb = m0 + wr * RW + rl;  // row of m-tile i: mb + 16 i
     float s[MT] = {};
@@ -493,14 +417,13 @@ __global__ __launch_bounds__(256 * WM, 1) void k_gemm_rln(const uint16_t* __rest
   }
 }
 
-// Selectable forms (NOMIC_RLN), all PIPE 2 (3 W stages, 2 A stages) with DMA interleave 2: 242
-// (default) = residual added in the epilogue, 16-B residual loads and output stores; 222 = the
-// same with 8-B loads and stores (the default until the 16-B form: mixed step 11.89-11.92 ->
-// 11.69-11.74 ms, profiles/encoder_tails); 232 = 222 with the residual added during the
-// K loop at K = 768 (EPI 3): 10 % faster on the o-proj with a cold residual (profiles/r4aq), but in
-// the encoder the residual was just written by the previous layer and is warm, and the mixed step
-// measured 12.452 (222) vs 12.500 ms (232) over three alternating runs each (profiles/r4ax).  The
-// other A/B forms of round 3 are gone; their measurements stay in profiles/r3_rln_*.
+// Selectable forms (NOMIC_RLN): 242 (default) = residual added in the epilogue, 16-B residual
+// loads and output stores (EPI 4); 222 = the same with 8-B loads and stores (EPI 0; the default
+// until the 16-B form: mixed step 11.89-11.92 -> 11.69-11.74 ms, profiles/encoder_tails); 232 = 222
+// with the residual added during the K loop at K = 768 (EPI 3): 10 % faster on the o-proj with a
+// cold residual (profiles/r4aq), but in the encoder the residual was just written by the previous
+// layer and is warm, and the mixed step measured 12.452 (222) vs 12.500 ms (232) over three
+// alternating runs each (profiles/r4ax).
 int g_rln_variant = -1;
 int rln_pick(int v) { return v == 222 || v == 232 ? v : 242; }
 int rln_variant() {
@@ -511,18 +434,17 @@ int rln_variant() {
   return g_rln_variant;
 }
 
-template <int PIPE, int EPI, int WM = 2, int ILV = 0, int PF = 1, bool AS = false, bool ROT = false>
+template <int EPI>
 void launch_rln(unsigned blocks, hipStream_t s, const uint16_t* A, long lda, const uint16_t* W, long ldw, int K, long M,
                 const uint16_t* res, long ldr, const uint16_t* gamma, const uint16_t* beta, float eps, uint16_t* out,
                 long ldo) {
   static bool attr = [] {
-    (void)hipFuncSetAttribute((const void*)k_gemm_rln<PIPE, EPI, WM, ILV, PF, AS, ROT>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              lds_bytes<PIPE>());
+    (void)hipFuncSetAttribute((const void*)k_gemm_rln<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
     return true;
   }();
   (void)attr;
-  hipLaunchKernelGGL((k_gemm_rln<PIPE, EPI, WM, ILV, PF, AS, ROT>), dim3(blocks), dim3(256 * WM), lds_bytes<PIPE>(), s, A, lda, W, ldw, K,
-                     M, res, ldr, gamma, beta, eps, out, ldo);
+  hipLaunchKernelGGL(k_gemm_rln<EPI>, dim3(blocks), dim3(kThreads), kLdsBytes, s, A, lda, W, ldw, K, M, res, ldr, gamma,
+                     beta, eps, out, ldo);
 }
 
 }  // namespace
@@ -537,7 +459,6 @@ extern "C" int nomic_gemm_res_ln(const void* A, long lda, const void* W, long ld
   if (lda % 8 || ldw % 8 || ldr % 4 || ldo % 4 || lda < K || ldw < K || ldr < N || ldo < N)
     return (int)hipErrorInvalidValue;
   if ((M - 1) * lda + K >= (1L << 32) || (long)kN * ldw >= (1L << 32)) return (int)hipErrorInvalidValue;
-  static_assert(lds_bytes<2>() <= 160 * 1024, "LDS budget");
   const unsigned blocks = (unsigned)((M + kBM - 1) / kBM);
   const auto* a = (const uint16_t*)A;
   const auto* w = (const uint16_t*)W;
@@ -550,9 +471,9 @@ extern "C" int nomic_gemm_res_ln(const void* A, long lda, const void* W, long ld
   int v = rln_variant();
   if (v == 232 && !(K / kBK >= 24 && K <= 768)) v = 222;
   if (v == 242 && !wide_ok) v = 222;
-  if (v == 232) launch_rln<2, 3, 2, 2>(blocks, s, a, lda, w, ldw, K, M, r, ldr, g, b, eps, o, ldo);
-  else if (v == 242) launch_rln<2, 4, 2, 2>(blocks, s, a, lda, w, ldw, K, M, r, ldr, g, b, eps, o, ldo);
-  else launch_rln<2, 0, 2, 2>(blocks, s, a, lda, w, ldw, K, M, r, ldr, g, b, eps, o, ldo);
+  if (v == 232) launch_rln<3>(blocks, s, a, lda, w, ldw, K, M, r, ldr, g, b, eps, o, ldo);
+  else if (v == 242) launch_rln<4>(blocks, s, a, lda, w, ldw, K, M, r, ldr, g, b, eps, o, ldo);
+  else launch_rln<0>(blocks, s, a, lda, w, ldw, K, M, r, ldr, g, b, eps, o, ldo);
   return (int)hipGetLastError();
 }
 

@@ -88,14 +88,10 @@ __global__ __launch_bounds__(256) void k_ln(const uint16_t* __restrict__ x, cons
   }
 }
 
-// ------------------------------------------------------------ attention --
-// One workgroup = 64 query rows of one (sequence, head); 4 waves x 16 rows.
-// Per 64-key tile: S = Q K^T (8 x mfma 16x16x32), online softmax in fp32
-// (exp2 with the scale folded in), P -> LDS (bf16) -> A operand, O += P V
-// with V staged transposed in LDS so the B fragment is one 16-B read.
-constexpr int AQ = 64, AK = 64, HD = 64;
+constexpr int HD = 64;  // head dim
 
-// ---------------------------------------------------------- attention v2 --
+// ------------------------------------------- attention, 16x16 MFMA form --
+// k_attn2: the completion daemon's causal prefill (grouped heads) and the encoder's fallback form.
 // One workgroup = 128 query rows of one (sequence, head); 4 waves x 32 rows
 // (two 16-row q-blocks per wave).  "Swapped" products keep every per-query
 // quantity lane-local (guide §3 accumulator-as-operand, T10, T12):
@@ -119,11 +115,9 @@ typedef __attribute__((address_space(3))) v4i16 lds_v4i16;
 __device__ __forceinline__ int ksw(int key, int c) { return c ^ (key & 7); }
 __device__ __forceinline__ int vsw(int key, int c) { return c ^ (((key >> 1) & 3) << 1); }
 
-// W = minimum waves per SIMD the register allocation must allow (0: unconstrained, 236 VGPRs ->
-// 2 waves/SIMD; 3: 168 VGPRs, 3 waves/SIMD, 12 waves per CU to hide the softmax/LDS latency)
-// XR: 1-D grid of nqb*heads blocks through the bijective XCD remap (guide §5 T1), so the q-blocks
+// 1-D grid of nqb*heads blocks through the bijective XCD remap (guide §5 T1), so the q-blocks
 // of one (sequence, head) -- which all stream the same K/V -- run on ONE XCD and share its L2
-// (with the 2-D grid consecutive q-blocks are dealt round-robin to 4 different XCDs and every
+// (with a 2-D grid consecutive q-blocks are dealt round-robin to 4 different XCDs and every
 // K/V tile is fetched from the fabric once per q-block).
 // Cross-lane reductions over the 4 lane groups g = lane >> 4 (a value of query column li sits in
 // lanes li, li+16, li+32, li+48): v_permlane16_swap / v_permlane32_swap (gfx950 VALU half-row
@@ -143,31 +137,34 @@ __device__ __forceinline__ float xg_sum(float x) {
 }
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-// OPT: permlane reductions, packed (v_pk_fma/v_pk_add) score scaling and row sums, and K/V
-// source pointers advanced per tile instead of recomputed with 64-bit multiplies.
+// Score scaling and row sums are packed (v_pk_fma / v_pk_add), and the K/V source pointers are
+// advanced per tile instead of recomputed with 64-bit multiplies.
 // CAUSAL: query row i of a sequence sees keys 0..i (the completion daemon's prefill, K18); key
 // tiles past the block's last row are skipped, the diagonal tiles masked per score.  kv_heads <
 // heads: grouped-query attention, q head h reads kv head h / (heads / kv_heads); the qkv rows are
 // [q (heads) | k (kv_heads) | v (kv_heads)] x HD.
-// LATE: the next tile's K/V global loads are issued after this tile's S^T = K Q^T MFMAs instead of
-// before them (the split async stage of cdna_hip_programming.md T14: the loads' issue no longer sits
-// between the barrier and the first MFMA, and their registers are live for half the tile).
-template <int W, bool XR = false, bool OPT = false, bool CAUSAL = false, int KT = 64, int QW = 4, bool LATE = false>
-__global__ __launch_bounds__(64 * QW) __attribute__((amdgpu_waves_per_eu(W > 0 ? W : 1))) void k_attn2(
+//
+// Measured and removed (each was a template parameter; 64 sequences x 512 tokens, TFLOP/s):
+//   - the 2-D grid without the XCD remap, shuffle (ds_bpermute) reductions with a scalar exp path
+//     and per-load address arithmetic, and an allocation held to 3 waves per SIMD (168 VGPRs): the
+//     steps between variants 2 and 6, 511 -> 537 (profiles/r1_attn_ab.jsonl)
+//   - 128-key tiles (KT 128): 380-395 against 541, 284 registers force one wave per SIMD
+//     (profiles/r2_attn_kt128_ab.jsonl)
+//   - 8 waves over 256-row q-blocks (QW 8): 483 against 513 (profiles/r2_attn_8wave_ab.jsonl)
+//   - the next tile's K/V loads issued after the S^T MFMAs instead of before them (LATE): 539
+//     against 546, +-1 % on every form (profiles/r3_attn_late_load_ab.jsonl)
+template <bool CAUSAL>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1))) void k_attn2(
     const uint16_t* __restrict__ qkv, uint16_t* __restrict__ out,
                                                const int32_t* __restrict__ cu, const int32_t* __restrict__ qblocks,
                                                int heads, float scale_log2, int kv_heads) {
+  constexpr int KT = 64;
   __shared__ __attribute__((aligned(16))) char lds[2][2][KT * 128];  // [buf][K | V][key * 128 B]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 4, li = lane & 15;
-  int qbi = blockIdx.x, head = blockIdx.y;
-  if constexpr (XR) {
-    const int nwg = gridDim.x, orig = blockIdx.x, q8 = nwg / 8, r8 = nwg % 8, xcd = orig % 8;
-    const int lid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + orig / 8;
-    const int nqb = nwg / heads;
-    head = lid / nqb;
-    qbi = lid - head * nqb;
-  }
+  const int nwg = gridDim.x, orig = blockIdx.x, q8 = nwg / 8, r8 = nwg % 8, xcd = orig % 8;
+  const int lid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + orig / 8;
+  const int nqb = nwg / heads, head = lid / nqb, qbi = lid - head * nqb;
   const int seq = qblocks[2 * qbi], qstart = qblocks[2 * qbi + 1];
   const long s0 = cu[seq], len = cu[seq + 1] - s0;
   const long ld = (long)(heads + 2 * kv_heads) * HD;
@@ -192,13 +189,11 @@ __global__ __launch_bounds__(64 * QW) __attribute__((amdgpu_waves_per_eu(W > 0 ?
     for (int qb = 0; qb < 2; ++qb) o[db][qb] = f32x4{0.f, 0.f, 0.f, 0.f};
   float m[2] = {-1e30f, -1e30f}, l[2] = {0.f, 0.f};
 
-  // QW waves: the block covers 32 * QW query rows; NT threads stage a K/V tile in NL rounds of
-  // NT / 8 keys (8 16-B chunks per 128-B key row)
-  constexpr int NT = 64 * QW, NL = KT * 8 / NT, KS = KT == 128 ? 7 : 6;  // KS = log2 KT
-  static_assert(KT == 64 || KT == 128, "key tile");
-  static_assert(QW == 4 || QW == 8, "waves per block");
+  // 64-key tiles; the block's NT threads (4 waves, 128 query rows) stage a K/V tile in NL rounds
+  // of NT / 8 keys (8 16-B chunks per 128-B key row)
+  constexpr int NT = 256, NL = KT * 8 / NT, KS = 6;  // KS = log2 KT
   uint4 rk[NL], rv[NL];
-  // OPT: per-lane K/V source pointers of tile 0, advanced by KT rows per tile
+  // per-lane K/V source pointers of tile 0, advanced by KT rows per tile
   // (lane load `it` sits NT / 8 keys after load 0: a wave-uniform offset, so one pointer pair per lane)
   const uint16_t* kp = Kg + (s0 + (tid >> 3)) * ld + (tid & 7) * 8;
   const uint16_t* vp = Vg + (s0 + (tid >> 3)) * ld + (tid & 7) * 8;
@@ -206,16 +201,11 @@ __global__ __launch_bounds__(64 * QW) __attribute__((amdgpu_waves_per_eu(W > 0 ?
   auto gload = [&](long k0) {
 #pragma unroll
     for (int it = 0; it < NL; ++it) {
-      const int c = tid + it * NT, key = c >> 3, ch = c & 7;
+      const int key = (tid + it * NT) >> 3;
       if (k0 + key < len) {
-        if constexpr (OPT) {
-          const long off = (k0 >> KS) * tstride + it * (NT / 8) * ld;
-          rk[it] = *(const uint4*)(kp + off);
-          rv[it] = *(const uint4*)(vp + off);
-        } else {
-          rk[it] = *(const uint4*)(Kg + (s0 + k0 + key) * ld + ch * 8);
-          rv[it] = *(const uint4*)(Vg + (s0 + k0 + key) * ld + ch * 8);
-        }
+        const long off = (k0 >> KS) * tstride + it * (NT / 8) * ld;
+        rk[it] = *(const uint4*)(kp + off);
+        rv[it] = *(const uint4*)(vp + off);
       } else {
         rk[it] = make_uint4(0, 0, 0, 0);
         rv[it] = make_uint4(0, 0, 0, 0);
@@ -232,7 +222,7 @@ __global__ __launch_bounds__(64 * QW) __attribute__((amdgpu_waves_per_eu(W > 0 ?
   };
 
   int ntiles = (int)((len + KT - 1) / KT);
-  if constexpr (CAUSAL) ntiles = min(ntiles, (int)((qstart + 32 * QW + KT - 1) / KT));
+  if constexpr (CAUSAL) ntiles = min(ntiles, (int)((qstart + 128 + KT - 1) / KT));
   gload(0);
   lwrite(0);
   __syncthreads();
@@ -240,7 +230,7 @@ __global__ __launch_bounds__(64 * QW) __attribute__((amdgpu_waves_per_eu(W > 0 ?
   for (int t = 0; t < ntiles; ++t) {
     const int buf = t & 1;
     const long k0 = (long)t * KT;
-    if (!LATE && t + 1 < ntiles) gload(k0 + KT);
+    if (t + 1 < ntiles) gload(k0 + KT);
     const char* Ks = lds[buf][0];
     const char* Vs = lds[buf][1];
     // ---- S^T = K Q^T
@@ -259,7 +249,6 @@ __global__ __launch_bounds__(64 * QW) __attribute__((amdgpu_waves_per_eu(W > 0 ?
           s[kb][qb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[kk], qf[qb][kk], s[kb][qb], 0, 0, 0);
       }
     }
-    if (LATE && t + 1 < ntiles) gload(k0 + KT);
     // ---- online softmax, one query per lane column.  Max on the raw scores (scale > 0), one
     // FMA per score into the exp2 domain, raw v_exp_f32 (no denormal fix-up: p underflows to 0),
     // key mask only on the sequence's partial last tile, and the deferred rescale of T13
@@ -290,12 +279,7 @@ __global__ __launch_bounds__(64 * QW) __attribute__((amdgpu_waves_per_eu(W > 0 ?
       float mx = -1e30f;
 #pragma unroll
       for (int kb = 0; kb < KT / 16; ++kb) mx = fmaxf(fmaxf(mx, fmaxf(s[kb][qb][0], s[kb][qb][1])), fmaxf(s[kb][qb][2], s[kb][qb][3]));
-      if constexpr (OPT) {
-        mx = xg_max(mx);
-      } else {
-        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-      }
+      mx = xg_max(mx);
       const float mxs = mx * scale_log2;
       if (!__all(mxs - m[qb] <= kThr)) {  // wave-uniform: rescale O and l once to the new max
         const float mn = fmaxf(m[qb], mxs);
@@ -306,35 +290,21 @@ __global__ __launch_bounds__(64 * QW) __attribute__((amdgpu_waves_per_eu(W > 0 ?
         for (int db = 0; db < 4; ++db) o[db][qb] *= alpha;
       }
       const float nm = -m[qb];
-      float ps = 0.f;
-      if constexpr (OPT) {
-        const f32x2 sc2 = {scale_log2, scale_log2}, nm2 = {nm, nm};
-        f32x2 acc2 = {0.f, 0.f};
+      const f32x2 sc2 = {scale_log2, scale_log2}, nm2 = {nm, nm};
+      f32x2 acc2 = {0.f, 0.f};
 #pragma unroll
-        for (int kb = 0; kb < KT / 16; ++kb)
+      for (int kb = 0; kb < KT / 16; ++kb)
 #pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            f32x2 x = {s[kb][qb][2 * h], s[kb][qb][2 * h + 1]};
-            x = x * sc2 + nm2;  // v_pk_fma_f32
-            x.x = __builtin_amdgcn_exp2f(x.x);
-            x.y = __builtin_amdgcn_exp2f(x.y);
-            s[kb][qb][2 * h] = x.x;
-            s[kb][qb][2 * h + 1] = x.y;
-            acc2 += x;  // v_pk_add_f32
-          }
-        ps = xg_sum(acc2.x + acc2.y);
-      } else {
-#pragma unroll
-        for (int kb = 0; kb < KT / 16; ++kb)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float p = __builtin_amdgcn_exp2f(fmaf(s[kb][qb][r], scale_log2, nm));
-            s[kb][qb][r] = p;
-            ps += p;
-          }
-        ps += __shfl_xor(ps, 16, 64);
-        ps += __shfl_xor(ps, 32, 64);
-      }
+        for (int h = 0; h < 2; ++h) {
+          f32x2 x = {s[kb][qb][2 * h], s[kb][qb][2 * h + 1]};
+          x = x * sc2 + nm2;  // v_pk_fma_f32
+          x.x = __builtin_amdgcn_exp2f(x.x);
+          x.y = __builtin_amdgcn_exp2f(x.y);
+          s[kb][qb][2 * h] = x.x;
+          s[kb][qb][2 * h + 1] = x.y;
+          acc2 += x;  // v_pk_add_f32
+        }
+      const float ps = xg_sum(acc2.x + acc2.y);
       l[qb] += ps;
     }
     // ---- O^T += V^T P^T, two 32-key steps
@@ -402,15 +372,19 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 __device__ __forceinline__ int k3sw(int key, int c) { return c ^ ((key >> 1) & 7); }
 __device__ __forceinline__ int v3sw(int key, int c) { return c ^ (((key >> 1) & 1) << 2); }
 
-// PF2: K/V global loads issued two tiles ahead (two register stages) instead of one, so a tile's
-// loads have two tiles' compute to land before their LDS write.
+// Measured and removed: K/V global loads issued two tiles ahead through a second register stage
+// (PF2), one of the forms this one beat: 530 and 614 against 634 TFLOP/s (variants 14 and 15 in
+// profiles/r3_attn_k_attn3_ab.jsonl).
 // (Measured in round 6 and not kept: the next tile's K/V loads issued after the QK^T MFMAs, and
 // s_setprio 1 over the MFMA runs -- alone and together within +-1.5 % of this form in isolation and
 // 0.1 % in the encoder, profiles/r6/README.md.  Also measured then and not kept: the two S^T chains
 // interleaved with four-way partial max / sum chains (neutral), and no row max after the first tile
 // with an overflow-guarded exact path (-2 % in isolation, neutral in the encoder), attn_forms2_ab; and
 // W = 4, four waves per SIMD at <= 128 VGPRs with 13 spilled: 105 vs 84 us per layer.)
-template <bool PF2 = false, int W = 1>
+// W (minimum waves per SIMD the allocation must allow) has the one value 1.  It stays a template
+// parameter because a plain kernel is emitted ahead of this file's kernel templates, which moves
+// this kernel's code in the object and renumbers its labels (profiles/kernel_prune/README.md).
+template <int W = 1>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W))) void k_attn3(const uint16_t* __restrict__ qkv, uint16_t* __restrict__ out,
                                                const int32_t* __restrict__ cu, const int32_t* __restrict__ qblocks,
                                                int heads, float scale_log2) {
@@ -441,46 +415,39 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W))) void k
     for (int r = 0; r < 16; ++r) o[db][r] = 0.f;
   float m = -1e30f, l = 0.f;
 
-  constexpr int NS = PF2 ? 2 : 1;  // register stages
-  uint4 rk[NS][NL], rv[NS][NL];
-  auto gload = [&](int stg, long k0) {
+  uint4 rk[NL], rv[NL];
+  auto gload = [&](long k0) {
 #pragma unroll
     for (int it = 0; it < NL; ++it) {
       const int c = tid + it * NT, key = c >> 3, ch = c & 7;
       if (k0 + key < len) {
-        rk[stg][it] = *(const uint4*)(Kg + (s0 + k0 + key) * ld + ch * 8);
-        rv[stg][it] = *(const uint4*)(Vg + (s0 + k0 + key) * ld + ch * 8);
+        rk[it] = *(const uint4*)(Kg + (s0 + k0 + key) * ld + ch * 8);
+        rv[it] = *(const uint4*)(Vg + (s0 + k0 + key) * ld + ch * 8);
       } else {
-        rk[stg][it] = make_uint4(0, 0, 0, 0);
-        rv[stg][it] = make_uint4(0, 0, 0, 0);
+        rk[it] = make_uint4(0, 0, 0, 0);
+        rv[it] = make_uint4(0, 0, 0, 0);
       }
     }
   };
-  auto lwrite = [&](int stg, int buf) {
+  auto lwrite = [&](int buf) {
 #pragma unroll
     for (int it = 0; it < NL; ++it) {
       const int c = tid + it * NT, key = c >> 3, ch = c & 7;
-      *(uint4*)(lds[buf][0] + key * 128 + (k3sw(key, ch) << 4)) = rk[stg][it];
-      *(uint4*)(lds[buf][1] + key * 128 + (v3sw(key, ch) << 4)) = rv[stg][it];
+      *(uint4*)(lds[buf][0] + key * 128 + (k3sw(key, ch) << 4)) = rk[it];
+      *(uint4*)(lds[buf][1] + key * 128 + (v3sw(key, ch) << 4)) = rv[it];
     }
   };
 
   const int ntiles = (int)((len + KT - 1) / KT);
-  gload(0, 0);
-  lwrite(0, 0);
-  if (PF2 && ntiles > 1) gload(1 % NS, KT);  // tile 1 rides one stage ahead of the loop's loads
+  gload(0);
+  lwrite(0);
   __syncthreads();
-  auto tile = [&](int t, const int sl, const int snext) {
+  // (a lambda: hipcc allocates registers differently for the same text written as the loop's body,
+  // and this is the form that was measured)
+  auto tile = [&](int t) {
     const int buf = t & 1;
     const long k0 = (long)t * KT;
-    // sl: the stage this tile's loads go to; snext: the stage holding tile t+1 (PF2: t's
-    // stage parity is a compile-time constant of each unrolled call, so the register stages
-    // are never indexed at run time)
-    if (PF2) {
-      if (t + 2 < ntiles) gload(sl, k0 + 2 * KT);
-    } else if (t + 1 < ntiles) {
-      gload(0, k0 + KT);
-    }
+    if (t + 1 < ntiles) gload(k0 + KT);
     const char* Ks = lds[buf][0];
     const char* Vs = lds[buf][1];
     // ---- S^T = K Q^T: A = K rows (key kb*32 + q32, d 16 ks + 8 hi), B = Q^T
@@ -558,17 +525,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W))) void k
           o[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf, o[db], 0, 0, 0);
         }
       }
-    if (t + 1 < ntiles) lwrite(snext, buf ^ 1);
+    if (t + 1 < ntiles) lwrite(buf ^ 1);
     __syncthreads();
   };
-  if constexpr (PF2) {
-    for (int t = 0; t < ntiles; t += 2) {
-      tile(t, 0, 1);
-      if (t + 1 < ntiles) tile(t + 1, 1, 0);
-    }
-  } else {
-    for (int t = 0; t < ntiles; ++t) tile(t, 0, 0);
-  }
+  for (int t = 0; t < ntiles; ++t) tile(t);
   // ---- normalise; lane holds d = 32 db + 8 g + 4 hi + 0..3 (g = r >> 2) of query q32
   if (qrow < len) {
     const float inv = 1.f / l;
@@ -825,10 +785,10 @@ int nomic_attention(const void* qkv, void* out, const int32_t* cu, const int32_t
   if (heads * HD * 3 % 8) return (int)hipErrorInvalidValue;
   const float scale_log2 = scale * 1.4426950408889634f;
   if (g_attn_variant == 6)
-    hipLaunchKernelGGL((k_attn2<0, true, true>), dim3(nqb * heads), dim3(256), 0, s, (const uint16_t*)qkv,
+    hipLaunchKernelGGL(k_attn2<false>, dim3(nqb * heads), dim3(256), 0, s, (const uint16_t*)qkv,
                        (uint16_t*)out, cu, qblocks, heads, scale_log2, heads);
   else
-    hipLaunchKernelGGL(k_attn3<false>, dim3(nqb * heads), dim3(256), 0, s, (const uint16_t*)qkv, (uint16_t*)out, cu,
+    hipLaunchKernelGGL(k_attn3<>, dim3(nqb * heads), dim3(256), 0, s, (const uint16_t*)qkv, (uint16_t*)out, cu,
                        qblocks, heads, scale_log2);
   return (int)hipGetLastError();
 }
@@ -839,7 +799,7 @@ int dec_attn_prefill(const void* qkv, void* out, const int32_t* cu, const int32_
                      int kv_heads, float scale, hipStream_t s) {
   if (nqb <= 0) return 0;
   if (kv_heads <= 0 || heads % kv_heads || (heads + 2 * kv_heads) * HD % 8) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL((k_attn2<0, true, true, true>), dim3(nqb * heads), dim3(256), 0, s, (const uint16_t*)qkv,
+  hipLaunchKernelGGL(k_attn2<true>, dim3(nqb * heads), dim3(256), 0, s, (const uint16_t*)qkv,
                      (uint16_t*)out, cu, qblocks, heads, scale * 1.4426950408889634f, kv_heads);
   return (int)hipGetLastError();
 }
