@@ -10,7 +10,7 @@
 //
 //   dec_gemv      M = 1 projections of the decode step (optionally with the RMSNorm of x
 //                 fused in): weight rows streamed once with 16-B loads, 4 rows per wave in flight
-//   dec_embed_tok / dec_rope_kv / dec_sample
+//   dec_embed_tok / dec_rope_kv / dec_sample_ws
 //                 the rest of a decode step, driven by a device-resident state {pos, token,
 //                 step} so a whole step (all layers + sampling) can be captured once in a HIP
 //                 graph and replayed per token with no host arguments changing
@@ -24,6 +24,7 @@
 #include <cstdlib>
 #include <map>
 #include <mutex>
+#include <type_traits>
 
 namespace {
 
@@ -194,7 +195,6 @@ __global__ __launch_bounds__(kDecWaves * 64) void k_attn_decode(const uint16_t* 
 #pragma unroll
     for (int i = 0; i < DPL; ++i) acc[i] *= corr;
     const int nv = min(64, L - base);
-#pragma unroll 8
     for (int t = 0; t < nv; ++t) {
       const float pt = __shfl(p, t, 64);
       const uint16_t* vr = Vb + (long)(base + t) * ldkv;
@@ -223,11 +223,6 @@ __global__ __launch_bounds__(kDecWaves * 64) void k_attn_decode(const uint16_t* 
   }
 }
 
-
-// Split-L decode attention (flash-decoding) for long caches: grid (H, S), workgroup (h, j) of 4 waves
-// scores keys [j c, (j + 1) c) with c = ceil(L / S) rounded up to 64 and writes its unnormalised
-// partial (m, l, acc[hd]) to ws; k_attn_combine merges the S partials of a head.  One workgroup per
-// head streams the whole cache through one CU (164 GB/s at L = 8192, profiles/r2_decode_q4.md).
 // k_attn_decode_g: decode attention for caches of at most kSmallL keys (the single-workgroup regime).
 // One workgroup per KV head serves its G query heads, so every K / V row is read once for the group
 // instead of once per head, and no phase walks the keys one at a time:
@@ -236,7 +231,7 @@ __global__ __launch_bounds__(kDecWaves * 64) void k_attn_decode(const uint16_t* 
 //   softmax one wave per head: max, exp, sum over the keys in LDS
 //   P V     the same row pieces of V, U rows in flight, fp32 accumulators per (head, 8 dims), then a
 //           reduction over the 256/(hd/8) key groups through LDS.
-// The single-workgroup kernel below it walks each wave's 64 keys serially in P V (a shuffle and a
+// k_attn_decode above walks each wave's 64 keys serially in P V (a shuffle and a
 // 4-B load per key): 28 us per layer at a 300-key cache, llama-7B heads (profiles/r3_decode_splits_short_ctx.jsonl);
 // this kernel 11.5 us, q4 decode 0.715 -> 0.577 ms/token (profiles/r3_decode_attn_small_ab.jsonl).  A 16-wave form
 // (one load round per phase, shuffle + LDS reduction) measured slower: 14.1 us (r3_decode_attn_small_wide_ab.jsonl).
@@ -384,6 +379,13 @@ __global__ __launch_bounds__(256) void k_attn_decode_g(const uint16_t* __restric
   }
 }
 
+// Split-L decode attention (flash-decoding) for long caches: grid (H, S), workgroup (h, j) of 4 waves
+// scores keys [j c, (j + 1) c) with c = ceil(L / S) rounded up to 64 and writes its unnormalised
+// partial (m, l, acc[hd]) to ws; k_attn_combine merges the S partials of a head.  One workgroup per
+// head streams the whole cache through one CU (164 GB/s at L = 8192, profiles/r2_decode_q4.md).
+// The chunk walk is k_attn_decode's, written out again on purpose: moved into one inlined function,
+// even word for word, it allocates other registers in 8 of the 20 kernels
+// (profiles/decoder_prune/README.md).
 constexpr int kSplitWaves = 4;
 constexpr int kMaxSplits = 32;
 
@@ -461,7 +463,6 @@ __global__ __launch_bounds__(kSplitWaves * 64) void k_attn_decode_split(
       m[g] = mn;
     }
     const int nv = min(64, k1 - base);
-#pragma unroll 4
     for (int t = 0; t < nv; ++t) {
       const uint16_t* vr = Vb + (long)(base + t) * ldkv;
       float vv[DPL];
@@ -545,6 +546,45 @@ __device__ __forceinline__ float wave_max(float v) {
 constexpr int kGemvRows = 4;
 constexpr int kGemvMaxK = 16384;
 
+// The row map and the store epilogue shared by k_gemv and k_gemv_q4.  A wave's R weight rows serve
+// outputs o0, o0 + 1, ..: row r is output o0 + r, or with MODE 2 the up (r even) / gate (r odd) row
+// of output o0 + r / 2 in pack_upgate's 32-row blocks.
+template <int MODE, int R>
+__device__ __forceinline__ void gemv_rows(int o0, int nout, long (&rows)[R]) {
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    int o = o0 + (MODE == 2 ? r / 2 : r);
+    if (o >= nout) o = nout - 1;  // tail: recompute the last output, never stored twice
+    rows[r] = MODE == 2 ? (long)(32 * (o / 16) + (o % 16) + (r & 1) * 16) : (long)o;
+  }
+}
+// acc: the rows' wave-reduced dot products; lane i stores output o0 + i
+template <int MODE, int R>
+__device__ __forceinline__ void gemv_store(const float (&acc)[R], int o0, int nout, int lane, const uint16_t* res,
+                                           void* out) {
+  constexpr int outs = MODE == 2 ? R / 2 : R;
+  if (lane < outs) {
+    const int o = o0 + lane;
+    if (o < nout) {
+      float a0 = acc[0], a1 = acc[1];
+#pragma unroll
+      for (int r = 0; r < R; ++r)
+        if ((MODE == 2 ? r / 2 : r) == lane) {
+          if (MODE == 2) { if (r & 1) a1 = acc[r]; else a0 = acc[r]; }
+          else a0 = acc[r];
+        }
+      if constexpr (MODE == 4) {
+        ((float*)out)[o] = a0;
+      } else {
+        float y = a0;
+        if constexpr (MODE == 1) y += bf2f(res[o]);
+        if constexpr (MODE == 2) y = a0 * a1 / (1.f + __expf(-a1));
+        ((uint16_t*)out)[o] = __builtin_bit_cast(uint16_t, (__bf16)y);
+      }
+    }
+  }
+}
+
 template <int MODE, bool RMS>
 __global__ __launch_bounds__(256) void k_gemv(const uint16_t* __restrict__ x, const float* __restrict__ rw, float eps,
                                               const uint16_t* __restrict__ W, int K, int nout,
@@ -559,12 +599,7 @@ __global__ __launch_bounds__(256) void k_gemv(const uint16_t* __restrict__ x, co
   const int o0 = (blockIdx.x * 4 + wave) * outs;
   const bool active = o0 < nout;
   long rows[kGemvRows];
-#pragma unroll
-  for (int r = 0; r < kGemvRows; ++r) {
-    int o = o0 + (MODE == 2 ? r / 2 : r);
-    if (o >= nout) o = nout - 1;  // tail: recompute the last output, never stored twice
-    rows[r] = MODE == 2 ? (long)(32 * (o / 16) + (o % 16) + (r & 1) * 16) : (long)o;
-  }
+  gemv_rows<MODE>(o0, nout, rows);
   uint4 wv[kGemvRows];
   if (active && lane < nch) {
 #pragma unroll
@@ -617,26 +652,7 @@ __global__ __launch_bounds__(256) void k_gemv(const uint16_t* __restrict__ x, co
   }
 #pragma unroll
   for (int r = 0; r < kGemvRows; ++r) acc[r] = wave_sum(acc[r]);
-  if (lane < outs) {
-    const int o = o0 + lane;
-    if (o < nout) {
-      float a0 = acc[0], a1 = acc[1];
-#pragma unroll
-      for (int r = 0; r < kGemvRows; ++r)
-        if ((MODE == 2 ? r / 2 : r) == lane) {
-          if (MODE == 2) { if (r & 1) a1 = acc[r]; else a0 = acc[r]; }
-          else a0 = acc[r];
-        }
-      if constexpr (MODE == 4) {
-        ((float*)out)[o] = a0;
-      } else {
-        float y = a0;
-        if constexpr (MODE == 1) y += bf2f(res[o]);
-        if constexpr (MODE == 2) y = a0 * a1 / (1.f + __expf(-a1));
-        ((uint16_t*)out)[o] = __builtin_bit_cast(uint16_t, (__bf16)y);
-      }
-    }
-  }
+  gemv_store<MODE>(acc, o0, nout, lane, res, out);
 }
 
 // ---------------------------------------------------------------------------
@@ -666,8 +682,10 @@ __device__ __forceinline__ float q4dot8(uint32_t w, const float* x) {
 
 // y[n] = x . W[n, :] with W in Q4G32.  Structure of k_gemv: x (optionally RMS-normalised) staged
 // in LDS as fp32 together with its 32-group sums (the m term: sum_k (d q_k + m) x_k =
-// d sum_k q_k x_k + m sum_k x_k); each wave owns R (4 or 8) weight rows, each lane one 32-k group per row
+// d sum_k q_k x_k + m sum_k x_k); each wave owns kGemvRows weight rows, each lane one 32-k group per row
 // and iteration (one 16-B load of nibbles + one scale word per row).
+// Measured and removed: 8 rows per wave (SPL_Q4_ROWS=8: 222 VGPRs, 2 waves per SIMD), 0.788 against
+// 0.713 ms/token (profiles/r2_decode_q4.md, r2_q4_rows_ab.jsonl).
 constexpr int kGemvQ4MaxK = 16384;
 constexpr int kQ4Rec = kQ4Group + 4;  // LDS floats per group record
 
@@ -682,7 +700,7 @@ __device__ __forceinline__ float q8dot4(uint32_t w, const float* x) {
 // BITS 4: Q4G32 nibbles (16 B per group); BITS 8: Q8G32 bytes (32 B per group, the same (d, m)
 // words: w = d * u + m with u in 0..255) -- the >4-bit GGUF tensors (Q6_K / Q5_x / Q8_0 / F16) of a
 // mostly-4-bit file keep >= 6 bits instead of being re-gridded to 4
-template <int MODE, bool RMS, int R = kGemvRows, int BITS = 4>
+template <int MODE, bool RMS, int BITS>
 __global__ __launch_bounds__(256) void k_gemv_q4(const uint16_t* __restrict__ x, const float* __restrict__ rw,
                                                  float eps, const uint8_t* __restrict__ Wq,
                                                  const uint32_t* __restrict__ Wsm, int K, int nout,
@@ -692,6 +710,7 @@ __global__ __launch_bounds__(256) void k_gemv_q4(const uint16_t* __restrict__ x,
   // conflict-free (16-lane phases start on 16 distinct 4-bank quads).
   extern __shared__ __attribute__((aligned(16))) float xs[];
   __shared__ float red[4];
+  constexpr int R = kGemvRows;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nch = K >> 3, ng = K / kQ4Group;
   // this wave's weight rows, and its first group's weights requested BEFORE x is staged: the HBM
@@ -700,12 +719,7 @@ __global__ __launch_bounds__(256) void k_gemv_q4(const uint16_t* __restrict__ x,
   const int o0 = (blockIdx.x * 4 + wave) * outs;
   const bool active = o0 < nout;
   long rows[R];
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    int o = o0 + (MODE == 2 ? r / 2 : r);
-    if (o >= nout) o = nout - 1;  // tail: recompute the last output, never stored twice
-    rows[r] = MODE == 2 ? (long)(32 * (o / 16) + (o % 16) + (r & 1) * 16) : (long)o;
-  }
+  gemv_rows<MODE>(o0, nout, rows);
   constexpr int GV = BITS / 4;  // 16-B loads per group and row
   const long qrow = (long)K * BITS / 8;
   uint4 wq[R][GV];
@@ -806,26 +820,7 @@ __global__ __launch_bounds__(256) void k_gemv_q4(const uint16_t* __restrict__ x,
   }
 #pragma unroll
   for (int r = 0; r < R; ++r) acc[r] = wave_sum(acc[r]);
-  if (lane < outs) {
-    const int o = o0 + lane;
-    if (o < nout) {
-      float a0 = acc[0], a1 = acc[1];
-#pragma unroll
-      for (int r = 0; r < R; ++r)
-        if ((MODE == 2 ? r / 2 : r) == lane) {
-          if (MODE == 2) { if (r & 1) a1 = acc[r]; else a0 = acc[r]; }
-          else a0 = acc[r];
-        }
-      if constexpr (MODE == 4) {
-        ((float*)out)[o] = a0;
-      } else {
-        float y = a0;
-        if constexpr (MODE == 1) y += bf2f(res[o]);
-        if constexpr (MODE == 2) y = a0 * a1 / (1.f + __expf(-a1));
-        ((uint16_t*)out)[o] = __builtin_bit_cast(uint16_t, (__bf16)y);
-      }
-    }
-  }
+  gemv_store<MODE>(acc, o0, nout, lane, res, out);
 }
 
 // bf16 W [N, K] -> Q4G32 (one thread per 32-weight group): affine min/max grid, d and m rounded
@@ -985,11 +980,11 @@ __device__ __forceinline__ double uniform01(uint64_t seed, uint64_t n) {
 
 // top-p -> temperature -> categorical draw on the device (the reference's llama sampler chain,
 // splainference.cpp:272-279): the nucleus is the smallest set of the most probable tokens whose
-// probability reaches top_p, found as a logit threshold by bisection (no sort); the kept logits are
-// divided by temp and one token is drawn by an inclusive scan in index order.  One 1024-thread
-// workgroup; logits stay in L2 between the passes.  Writes state.token (and pos += inc_pos,
-// step += 1) and the token to `host_tok` (pinned, may be null).
+// probability reaches top_p, found as a logit threshold (no sort); the kept logits are divided by
+// temp and one token is drawn by an inclusive scan over the threads' masses.  Writes state.token
+// (and pos += inc_pos, step += 1) and the token to `host_tok` (pinned, may be null).
 constexpr int kSampThreads = 1024;
+constexpr int kSampRegs = 4;  // logits per thread: vocabularies up to 4096 tokens, longer ones run k_sb_*
 
 __device__ float block_reduce(float v, float* sh, bool is_max) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1002,135 +997,19 @@ __device__ float block_reduce(float v, float* sh, bool is_max) {
   return r;
 }
 
-__global__ __launch_bounds__(kSampThreads) void k_sample(const float* __restrict__ logits, int V,
-                                                         const uint8_t* __restrict__ mask, float top_p, float temp,
-                                                         uint64_t seed, int32_t* __restrict__ st, int inc_pos,
-                                                         int32_t* host_tok) {
-  __shared__ float sh[kSampThreads / 64];
-  __shared__ float scan[kSampThreads];
-  const int tid = threadIdx.x;
-  auto lg = [&](int i) { return (mask && !mask[i]) ? -INFINITY : logits[i]; };
-  float m = -INFINITY;
-#pragma unroll 8  // 8 logit loads in flight per thread (a rolled loop waits one L2 latency per element)
-  for (int i = tid; i < V; i += kSampThreads) m = fmaxf(m, lg(i));
-  const float M = block_reduce(m, sh, true);
-  float z = 0.f;
-#pragma unroll 8  // 8 logit loads in flight per thread (a rolled loop waits one L2 latency per element)
-  for (int i = tid; i < V; i += kSampThreads) z += __expf(lg(i) - M);
-  const float Z = block_reduce(z, sh, false);
-  // nucleus threshold t: the largest logit cut whose kept mass reaches top_p.  Found by two
-  // levels of a 1024-bin mass histogram over the current interval [lo, hi) (LDS float atomics),
-  // each level keeping the bin where the suffix mass crosses top_p * Z: 2 passes over the logits
-  // to a resolution of 40 / 2^20 (a few float ulps of a logit), instead of one pass per bisection
-  // step (24 passes: 163 us per token for a 32000-token vocabulary).
-  __shared__ float hist[kSampThreads];
-  // 8 copies of every bin, picked by lane & 7: flat logits (a random-init model: every logit in
-  // one or two bins) put a wave's 64 same-address LDS atomics into one 64-way conflict; the copies
-  // cut it to 8-way (83 -> ? us per token at V = 32000, profiles/r2_decode_q4.md)
-  __shared__ float hist8[kSampThreads * 8];
-  __shared__ int jstar;
-  float lo = M - 40.f;  // mass below M - 40 is < V e^-40
-  if (top_p < 1.f) {
-    const float target = top_p * Z;
-    float w = 40.f / kSampThreads * (1.f + 1e-6f);  // bin width: the top bin holds l == M
-    float above = 0.f;                              // mass at or above the interval's upper end
-    for (int level = 0; level < 2; ++level) {
-#pragma unroll
-      for (int c = 0; c < 8; ++c) hist8[c * kSampThreads + tid] = 0.f;
-      if (tid == 0) jstar = 0;
-      __syncthreads();
-      const float inv_w = 1.f / w, hi = lo + w * kSampThreads;
-#pragma unroll 8  // 8 logit loads in flight per thread (a rolled loop waits one L2 latency per element)
-      for (int i = tid; i < V; i += kSampThreads) {
-        const float l = lg(i);
-        if (l >= lo && l < hi) {
-          const int bin = min(kSampThreads - 1, (int)((l - lo) * inv_w));
-          atomicAdd(&hist8[bin * 8 + (tid & 7)], __expf(l - M));
-        }
-      }
-      __syncthreads();
-      {
-        float h = 0.f;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) h += hist8[tid * 8 + c];
-        hist[tid] = h;
-      }
-      __syncthreads();
-      for (int off = 1; off < kSampThreads; off <<= 1) {  // suffix sums: S[j] = mass(l >= lo + j w)
-        const float v = tid + off < kSampThreads ? hist[tid + off] : 0.f;
-        __syncthreads();
-        hist[tid] += v;
-        __syncthreads();
-      }
-      if (hist[tid] + above >= target) atomicMax(&jstar, tid);  // S is non-increasing: the last bin
-      __syncthreads();
-      const int j = jstar;
-      above += j + 1 < kSampThreads ? hist[j + 1] : 0.f;
-      lo += j * w;
-      w *= 1.f / kSampThreads;
-      __syncthreads();
-    }
-  } else {
-    lo = -INFINITY;
-  }
-  const float cut = lo;
-  const float it = 1.f / fmaxf(temp, 1e-6f);
-  // contiguous chunk per thread for the ordered scan
-  const int chunk = (V + kSampThreads - 1) / kSampThreads;
-  const int b = tid * chunk, e = min(V, b + chunk);
-  float part = 0.f;
-#pragma unroll 8  // 8 logit loads in flight per thread (a rolled loop waits one L2 latency per element)
-  for (int i = b; i < e; ++i) {
-    const float l = lg(i);
-    if (l >= cut) part += __expf((l - M) * it);
-  }
-  scan[tid] = part;
-  __syncthreads();
-  for (int off = 1; off < kSampThreads; off <<= 1) {  // Hillis-Steele inclusive scan
-    const float v = tid >= off ? scan[tid - off] : 0.f;
-    __syncthreads();
-    scan[tid] += v;
-    __syncthreads();
-  }
-  const float total = scan[kSampThreads - 1];
-  const float u = (float)(uniform01(seed, (uint64_t)st[ST_STEP]) * total);
-  const float before = tid ? scan[tid - 1] : 0.f;
-  __shared__ int pick;
-  if (tid == 0) pick = -1;
-  __syncthreads();
-  if (u >= before && u < scan[tid] && part > 0.f) {
-    float run = before;
-    int sel = -1;
-#pragma unroll 8  // 8 logit loads in flight per thread (a rolled loop waits one L2 latency per element)
-    for (int i = b; i < e; ++i) {
-      const float l = lg(i);
-      if (l < cut) continue;
-      sel = i;
-      run += __expf((l - M) * it);
-      if (u < run) break;
-    }
-    pick = sel;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    int t = pick;
-    if (t < 0) {  // u landed on a rounding gap at the very top: take the most probable token
-      for (int i = 0; i < V; ++i)
-        if (lg(i) == M) { t = i; break; }
-    }
-    st[ST_TOK] = t;
-    st[ST_POS] += inc_pos;
-    st[ST_STEP] += 1;
-    if (host_tok) __hip_atomic_store(host_tok, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
-}
-
-// The same sampler with the vocabulary held in registers (V <= 1024 * R): every pass reads the
-// thread's R logits from VGPRs instead of re-reading the logit vector (the global-memory form
-// above costs ~2.5 ns per logit per call: 82 us at V = 32000).  Thread t owns tokens t + 1024 k;
-// the categorical draw walks the threads' masses in that fixed order, which is a different but
-// equally valid order of the same distribution.
-template <int R>
+// One 1024-thread workgroup with the vocabulary held in registers (V <= 1024 * kSampRegs): thread t
+// owns tokens t + 1024 k and every pass reads them from VGPRs; the categorical draw walks the
+// threads' masses in that fixed order, an equally valid order of the same distribution.
+// Nucleus threshold: the largest logit cut whose kept mass reaches top_p, found by two levels of a
+// 1024-bin mass histogram over the current interval [lo, hi) (LDS float atomics), each level keeping
+// the bin where the suffix mass crosses top_p * Z: a resolution of 40 / 2^20 (a few float ulps of a
+// logit) instead of one pass per bisection step.  Every bin has 8 copies, picked by lane & 7: flat
+// logits (a random-init model: every logit in one or two bins) put a wave's 64 same-address LDS
+// atomics into one 64-way conflict; the copies cut it to 8-way (profiles/r2_decode_q4.md).
+// Measured and removed: the same sampler reading the logits from global memory in every pass
+// (k_sample, any V) and this one at 32 registers per thread (V <= 32768), both behind dec_sample,
+// which only a test called: 255-275 us at V = 128256 and 61-65 us at V = 32000 against 53 and
+// 47 us for the k_sb_* chain (profiles/r2_decode_q4.md).
 __global__ __launch_bounds__(kSampThreads) void k_sample_reg(const float* __restrict__ logits, int V,
                                                              const uint8_t* __restrict__ mask, float top_p,
                                                              float temp, uint64_t seed, int32_t* __restrict__ st,
@@ -1141,6 +1020,7 @@ __global__ __launch_bounds__(kSampThreads) void k_sample_reg(const float* __rest
   __shared__ float hist8[kSampThreads * 8];
   __shared__ int jstar, pick;
   const int tid = threadIdx.x;
+  constexpr int R = kSampRegs;
   float v[R];
   float m = -INFINITY;
 #pragma unroll
@@ -1154,7 +1034,7 @@ __global__ __launch_bounds__(kSampThreads) void k_sample_reg(const float* __rest
 #pragma unroll
   for (int k = 0; k < R; ++k) z += __expf(v[k] - M);
   const float Z = block_reduce(z, sh, false);
-  float lo = M - 40.f;  // nucleus cut: two levels of the replicated 1024-bin histogram (k_sample)
+  float lo = M - 40.f;  // nucleus cut: two levels of the replicated 1024-bin histogram; mass below M - 40 is < V e^-40
   if (top_p < 1.f) {
     const float target = top_p * Z;
     float w = 40.f / kSampThreads * (1.f + 1e-6f);
@@ -1297,7 +1177,7 @@ __global__ __launch_bounds__(kSbThreads) void k_sb_max(const float* __restrict__
   }
 }
 
-// B / D: block mass (level 0) and the mass histogram of [lo, lo + 1024 w) (replicated bins, k_sample)
+// B / D: block mass (level 0) and the mass histogram of [lo, lo + 1024 w) (replicated bins, as k_sample_reg)
 template <int LEVEL>
 __global__ __launch_bounds__(kSbThreads) void k_sb_hist(const float* __restrict__ logits, int V,
                                                         const uint8_t* __restrict__ mask, float* __restrict__ ws) {
@@ -1413,7 +1293,7 @@ __global__ __launch_bounds__(kSbThreads) void k_sb_part(const float* __restrict_
 }
 
 // G: the draw -- the block whose prefix range holds u, then inside its slice (thread t owns the
-// contiguous elements [t c, t c + c)) the token; state update as k_sample
+// contiguous elements [t c, t c + c)) the token; state update as k_sample_reg
 __global__ __launch_bounds__(kSbBins) void k_sb_draw(const float* __restrict__ logits, int V,
                                                      const uint8_t* __restrict__ mask, float temp, uint64_t seed,
                                                      const float* __restrict__ ws, int32_t* __restrict__ st,
@@ -1698,6 +1578,106 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
   }
 }
 
+// ------------------------------------------------------------------ host dispatch --
+template <int V>
+using ic = std::integral_constant<int, V>;
+
+// the runtime shape as compile-time constants: f(ic<D>) for d = head dim / 64 in 1..4, and
+// f(ic<D>, ic<G>) with g = heads per workgroup in {1, 2, 4, 8}
+template <class F>
+void with_d(int d, F f) {
+  switch (d) {
+    case 1: f(ic<1>{}); break;
+    case 2: f(ic<2>{}); break;
+    case 3: f(ic<3>{}); break;
+    default: f(ic<4>{}); break;
+  }
+}
+template <class F>
+void with_d_g(int d, int g, F f) {
+  with_d(d, [&](auto D) {
+    switch (g) {
+      case 2: f(D, ic<2>{}); break;
+      case 4: f(D, ic<4>{}); break;
+      case 8: f(D, ic<8>{}); break;
+      default: f(D, ic<1>{}); break;
+    }
+  });
+}
+
+// f(ic<MODE>, bool_constant<RMS>) for a GEMV epilogue mode (0, 1, 2, 4); false: no such mode
+template <class F>
+bool with_mode_rms(int mode, bool rms, F f) {
+  auto on_rms = [&](auto M) {
+    if (rms) f(M, std::true_type{});
+    else f(M, std::false_type{});
+  };
+  switch (mode) {
+    case 0: on_rms(ic<0>{}); return true;
+    case 1: on_rms(ic<1>{}); return true;
+    case 2: on_rms(ic<2>{}); return true;
+    case 4: on_rms(ic<4>{}); return true;
+    default: return false;
+  }
+}
+
+// dec_gemv over Q4G32 / Q8G32 weights (k_gemv_q4<.., BITS>)
+template <int BITS>
+int gemv_qn(int mode, const void* x, const float* rms_w, float eps, const void* Wq, const void* Wsm, int N, int K,
+            const void* res, void* out, hipStream_t s) {
+  if (K <= 0 || K % kQ4Group || K > kGemvQ4MaxK || N <= 0 || (mode == 2 && N % 32) || (mode == 1 && !res) ||
+      ((uintptr_t)Wq | (uintptr_t)x) % 16 || (uintptr_t)Wsm % 4 || (rms_w && (uintptr_t)rms_w % 16))
+    return (int)hipErrorInvalidValue;
+  const int nout = mode == 2 ? N / 2 : N;
+  const int per_block = 4 * (mode == 2 ? kGemvRows / 2 : kGemvRows);
+  const dim3 g((unsigned)((nout + per_block - 1) / per_block)), b(256);
+  const size_t lds = (size_t)(K / kQ4Group) * kQ4Rec * sizeof(float);
+  const bool known = with_mode_rms(mode, rms_w != nullptr, [&](auto M, auto R) {
+    hipLaunchKernelGGL((k_gemv_q4<M(), R(), BITS>), g, b, lds, s, (const uint16_t*)x, rms_w, eps, (const uint8_t*)Wq,
+                       (const uint32_t*)Wsm, K, nout, (const uint16_t*)res, out);
+  });
+  return known ? (int)hipGetLastError() : (int)hipErrorInvalidValue;
+}
+
+// the four quantise / dequantise entry points: W bf16 [N, K] row-major and contiguous, one thread per
+// 32-weight group; launch(grid, groups) starts the kernel
+template <class F>
+int quant_launch(const void* W, long N, int K, const void* Wq, const void* Wsm, F launch) {
+  if (N <= 0 || K <= 0 || K % kQ4Group || ((uintptr_t)W | (uintptr_t)Wq) % 16 || (uintptr_t)Wsm % 4)
+    return (int)hipErrorInvalidValue;
+  const long groups = N * (K / kQ4Group);
+  launch(dim3((unsigned)((groups + 255) / 256)), groups);
+  return (int)hipGetLastError();
+}
+
+// split-L workspace, one per stream (the decode step's layers run in order on one stream): H <= 128
+// heads x kMaxSplits partials of hd + 2 floats, allocated on first use (outside graph capture: the
+// decode engine runs one step eagerly before capturing)
+float* split_workspace(hipStream_t s) {
+  static std::mutex mu;
+  static std::map<hipStream_t, float*> table;
+  std::lock_guard<std::mutex> g(mu);
+  auto it = table.find(s);
+  if (it != table.end()) return it->second;
+  float* w = nullptr;
+  if (hipMalloc((void**)&w, (size_t)128 * kMaxSplits * (256 + 2) * sizeof(float)) != hipSuccess) return nullptr;
+  return table[s] = w;
+}
+
+// splits for a cache of (up to) L keys: the single-workgroup kernel up to 512 keys, then one split per
+// 256 keys, at most kMaxSplits (sweep over 4..32 splits at H 32 / KVH 8 / hd 128:
+// profiles/r2_decode_splits.jsonl)
+int decode_splits(int L) {
+  static const int env = [] {
+    const char* e = getenv("SPL_DEC_SPLITS");
+    return e && *e ? atoi(e) : -1;
+  }();
+  if (env >= 1) return env < kMaxSplits ? env : kMaxSplits;
+  if (L <= 512) return 1;
+  const int sp = (L + 255) / 256;
+  return sp > kMaxSplits ? kMaxSplits : sp;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1723,132 +1703,68 @@ int dec_attn_prefill_kv(const void* q, long ldq, const void* k, const void* v, l
   return (int)hipGetLastError();
 }
 
-// q: bf16 [H*hd] (one token, RoPE applied); k/v: bf16 cache rows [L, ldkv] (ldkv = KVH*hd);
-// out: bf16 [H*hd].  hd in {64, 128, 192, 256}, H % KVH == 0, L >= 1, 16-B aligned rows.
-int dec_attn_decode_st(const void* q, const void* k, const void* v, long ldkv, int L, int H, int KVH, int hd,
-                       float scale, void* out, const int32_t* st, hipStream_t s);
-int dec_attn_decode(const void* q, const void* k, const void* v, long ldkv, int L, int H, int KVH, int hd,
-                    float scale, void* out, hipStream_t s) {
-  return dec_attn_decode_st(q, k, v, ldkv, L, H, KVH, hd, scale, out, nullptr, s);
-}
-
-// as dec_attn_decode; with st != null the cache length is st[0] + 1 (L is ignored)
-// split-L workspace, one per stream (the decode step's layers run in order on one stream): H <= 128
-// heads x kMaxSplits partials of hd + 2 floats, allocated on first use (outside graph capture: the
-// decode engine runs one step eagerly before capturing)
-static float* split_workspace(hipStream_t s) {
-  static std::mutex mu;
-  static std::map<hipStream_t, float*> table;
-  std::lock_guard<std::mutex> g(mu);
-  auto it = table.find(s);
-  if (it != table.end()) return it->second;
-  float* w = nullptr;
-  if (hipMalloc((void**)&w, (size_t)128 * kMaxSplits * (256 + 2) * sizeof(float)) != hipSuccess) return nullptr;
-  return table[s] = w;
-}
-
-// splits for a cache of (up to) L keys: the single-workgroup kernel up to 512 keys, then one split per
-// 256 keys, at most kMaxSplits (sweep over 4..32 splits at H 32 / KVH 8 / hd 128:
-// profiles/r2_decode_splits.jsonl)
-static int decode_splits(int L) {
-  static const int env = [] {
-    const char* e = getenv("SPL_DEC_SPLITS");
-    return e && *e ? atoi(e) : -1;
-  }();
-  if (env >= 1) return env < kMaxSplits ? env : kMaxSplits;
-  if (L <= 512) return 1;
-  const int sp = (L + 255) / 256;
-  return sp > kMaxSplits ? kMaxSplits : sp;
-}
-
-int dec_attn_decode_ws(const void* q, const void* k, const void* v, long ldkv, int L, int H, int KVH, int hd,
-                       float scale, void* out, const int32_t* st, float* ws, hipStream_t s);
-int dec_attn_decode_st(const void* q, const void* k, const void* v, long ldkv, int L, int H, int KVH, int hd,
-                       float scale, void* out, const int32_t* st, hipStream_t s) {
-  return dec_attn_decode_ws(q, k, v, ldkv, L, H, KVH, hd, scale, out, st, nullptr, s);
-}
-
-// dec_attn_decode_st with a caller-owned split workspace ws (H * 32 * (hd + 2) floats; null: a
-// per-stream one allocated on first use -- a graph-captured step must pass its own, since nothing
-// may be allocated during capture)
+// Single-token decode attention.  q: bf16 [H*hd] (one token, RoPE applied); k/v: bf16 cache rows
+// [L, ldkv] (ldkv = KVH*hd); out: bf16 [H*hd].  hd in {64, 128, 192, 256}, H % KVH == 0, L >= 1, 16-B
+// aligned rows.  With st != null the cache length is st[0] + 1, read on the device, and L is the cache
+// CAPACITY (it sizes the split count).  ws: the caller's split workspace (H * 32 * (hd + 2) floats);
+// null: a per-stream one allocated on first use -- a graph-captured step must pass its own, since
+// nothing may be allocated during capture.
+// Kernel choice: head dims 64 / 128 / 256 with a query-group size of 1, 2, 4 or 8 run the grouped
+// three-phase kernel (k_attn_decode_g), whole up to kSmallL keys and as the splits of longer caches;
+// every other shape walks the keys (k_attn_decode, k_attn_decode_split).
+// Measured and removed: SPL_DEC_SMALL=0, which put the grouped shapes back on the walking kernels:
+// 28 against 11.5 us per layer at a 300-key cache, q4 decode 0.715 against 0.577 ms/token
+// (profiles/r3_decode_attn_small_ab.jsonl).
 int dec_attn_decode_ws(const void* q, const void* k, const void* v, long ldkv, int L, int H, int KVH, int hd,
                        float scale, void* out, const int32_t* st, float* ws, hipStream_t s) {
-  // with st, L is the cache CAPACITY (sizes the split count; the length itself is read on the device)
   if (L <= 0 || H <= 0 || KVH <= 0 || H % KVH || hd <= 0 || hd % 64 || hd > 256 || ldkv % 8 ||
       ldkv < (long)KVH * hd || ((uintptr_t)k | (uintptr_t)v) % 16)
     return (int)hipErrorInvalidValue;
   const int grp = H / KVH;
   const int S = decode_splits(L);
-  // SPL_DEC_SMALL: caches of at most kSmallL keys on the grouped three-phase kernel, and the splits of longer
-  // ones on its split form (chunks of at most kSmallL keys); 0 = the per-head / per-group walking kernels
-  static const int small = [] {
-    const char* e = getenv("SPL_DEC_SMALL");
-    return e && *e ? atoi(e) : 1;
-  }();
-  const bool grouped = small && (hd == 64 || hd == 128 || hd == 256) && (grp == 1 || grp == 2 || grp == 4 || grp == 8);
+  const bool grouped = (hd == 64 || hd == 128 || hd == 256) && (grp == 1 || grp == 2 || grp == 4 || grp == 8);
+  const uint16_t *qq = (const uint16_t*)q, *kk = (const uint16_t*)k, *vv = (const uint16_t*)v;
+  uint16_t* oo = (uint16_t*)out;
   if (S > 1 && H <= 128) {
     if (!ws) ws = split_workspace(s);
     if (!ws) return (int)hipErrorOutOfMemory;
     if (grouped && ((L + S - 1) / S + 63) / 64 * 64 <= kSmallL) {
-      const uint16_t *qq = (const uint16_t*)q, *kk = (const uint16_t*)k, *vv = (const uint16_t*)v;
-      const dim3 gg((unsigned)KVH, (unsigned)S), bb(256);
-#define GSPLIT(D_, G_) hipLaunchKernelGGL((k_attn_decode_g<D_, G_, true>), gg, bb, 0, s, qq, kk, vv, ldkv, L, scale, \
-                                          (uint16_t*)nullptr, st, ws)
-#define GSPLIT_G(D_) switch (grp) { case 1: GSPLIT(D_, 1); break; case 2: GSPLIT(D_, 2); break; \
-                                    case 4: GSPLIT(D_, 4); break; default: GSPLIT(D_, 8); break; }
-      switch (hd) {
-        case 64: GSPLIT_G(1); break;
-        case 128: GSPLIT_G(2); break;
-        default: GSPLIT_G(4); break;
-      }
-#undef GSPLIT_G
-#undef GSPLIT
-      hipLaunchKernelGGL(k_attn_combine, dim3((unsigned)H), dim3(256), 0, s, ws, S, hd, (uint16_t*)out);
-      return (int)hipGetLastError();
+      with_d_g(hd / 64, grp, [&](auto D, auto G) {
+        if constexpr (D() != 3)
+          hipLaunchKernelGGL((k_attn_decode_g<D(), G(), true>), dim3((unsigned)KVH, (unsigned)S), dim3(256), 0, s, qq,
+                             kk, vv, ldkv, L, scale, (uint16_t*)nullptr, st, ws);
+      });
+    } else {
+      // heads per workgroup: the whole kv group when it is 2, 4 or 8 heads (shared K/V rows), else 1
+      const int wg = (grp == 2 || grp == 4 || grp == 8) ? grp : 1;
+      with_d_g(hd / 64, wg, [&](auto D, auto G) {
+        hipLaunchKernelGGL((k_attn_decode_split<D(), G()>), dim3((unsigned)(H / G()), (unsigned)S),
+                           dim3(kSplitWaves * 64), 0, s, qq, kk, vv, ldkv, L, grp, scale, ws, st);
+      });
     }
-    // heads per workgroup: the whole kv group when it is 2, 4 or 8 heads (shared K/V rows), else 1
-    const int G = (grp == 2 || grp == 4 || grp == 8) ? grp : 1;
-    const dim3 gs((unsigned)(H / G), (unsigned)S), bs(kSplitWaves * 64);
-    const uint16_t *qq = (const uint16_t*)q, *kk = (const uint16_t*)k, *vv = (const uint16_t*)v;
-#define SPLIT(D_, G_) hipLaunchKernelGGL((k_attn_decode_split<D_, G_>), gs, bs, 0, s, qq, kk, vv, ldkv, L, grp, scale, ws, st)
-#define SPLIT_G(D_) switch (G) { case 2: SPLIT(D_, 2); break; case 4: SPLIT(D_, 4); break; \
-                                 case 8: SPLIT(D_, 8); break; default: SPLIT(D_, 1); break; }
-    switch (hd / 64) {
-      case 1: SPLIT_G(1); break;
-      case 2: SPLIT_G(2); break;
-      case 3: SPLIT_G(3); break;
-      default: SPLIT_G(4); break;
-    }
-#undef SPLIT_G
-#undef SPLIT
-    hipLaunchKernelGGL(k_attn_combine, dim3((unsigned)H), dim3(256), 0, s, ws, S, hd, (uint16_t*)out);
-    return (int)hipGetLastError();
-  }
-  const uint16_t *qq = (const uint16_t*)q, *kk = (const uint16_t*)k, *vv = (const uint16_t*)v;
-  uint16_t* oo = (uint16_t*)out;
-  if (grouped && L <= kSmallL) {
-    const dim3 gg((unsigned)KVH), bb(256);
-#define SMALL(D_, G_) hipLaunchKernelGGL((k_attn_decode_g<D_, G_>), gg, bb, 0, s, qq, kk, vv, ldkv, L, scale, oo, st, \
-                                         (float*)nullptr)
-#define SMALL_G(D_) switch (grp) { case 1: SMALL(D_, 1); break; case 2: SMALL(D_, 2); break; \
-                                   case 4: SMALL(D_, 4); break; default: SMALL(D_, 8); break; }
-    switch (hd) {
-      case 64: SMALL_G(1); break;
-      case 128: SMALL_G(2); break;
-      default: SMALL_G(4); break;
-    }
-#undef SMALL_G
-#undef SMALL
-    return (int)hipGetLastError();
-  }
-  const dim3 g((unsigned)H), b(kDecWaves * 64);
-  switch (hd / 64) {
-    case 1: hipLaunchKernelGGL(k_attn_decode<1>, g, b, 0, s, qq, kk, vv, ldkv, L, grp, hd, scale, oo, st); break;
-    case 2: hipLaunchKernelGGL(k_attn_decode<2>, g, b, 0, s, qq, kk, vv, ldkv, L, grp, hd, scale, oo, st); break;
-    case 3: hipLaunchKernelGGL(k_attn_decode<3>, g, b, 0, s, qq, kk, vv, ldkv, L, grp, hd, scale, oo, st); break;
-    default: hipLaunchKernelGGL(k_attn_decode<4>, g, b, 0, s, qq, kk, vv, ldkv, L, grp, hd, scale, oo, st); break;
+    hipLaunchKernelGGL(k_attn_combine, dim3((unsigned)H), dim3(256), 0, s, ws, S, hd, oo);
+  } else if (grouped && L <= kSmallL) {
+    with_d_g(hd / 64, grp, [&](auto D, auto G) {
+      if constexpr (D() != 3)
+        hipLaunchKernelGGL((k_attn_decode_g<D(), G()>), dim3((unsigned)KVH), dim3(256), 0, s, qq, kk, vv, ldkv, L,
+                           scale, oo, st, (float*)nullptr);
+    });
+  } else {
+    with_d(hd / 64, [&](auto D) {
+      hipLaunchKernelGGL(k_attn_decode<D()>, dim3((unsigned)H), dim3(kDecWaves * 64), 0, s, qq, kk, vv, ldkv, L, grp,
+                         hd, scale, oo, st);
+    });
   }
   return (int)hipGetLastError();
+}
+
+int dec_attn_decode_st(const void* q, const void* k, const void* v, long ldkv, int L, int H, int KVH, int hd,
+                       float scale, void* out, const int32_t* st, hipStream_t s) {
+  return dec_attn_decode_ws(q, k, v, ldkv, L, H, KVH, hd, scale, out, st, nullptr, s);
+}
+int dec_attn_decode(const void* q, const void* k, const void* v, long ldkv, int L, int H, int KVH, int hd,
+                    float scale, void* out, hipStream_t s) {
+  return dec_attn_decode_ws(q, k, v, ldkv, L, H, KVH, hd, scale, out, nullptr, nullptr, s);
 }
 
 // x/out: bf16 rows (strides in elements), w: fp32 [d]; d % 8 == 0, 16-B aligned rows.
@@ -1886,61 +1802,15 @@ int dec_gemv(int mode, const void* x, const float* rms_w, float eps, const void*
   const int nout = mode == 2 ? N / 2 : N;
   const int per_block = 4 * (mode == 2 ? kGemvRows / 2 : kGemvRows);
   const dim3 g((unsigned)((nout + per_block - 1) / per_block)), b(256);
-  const uint16_t *xx = (const uint16_t*)x, *ww = (const uint16_t*)W, *rr = (const uint16_t*)res;
-#define GEMV(M_, R_) hipLaunchKernelGGL((k_gemv<M_, R_>), g, b, 0, s, xx, rms_w, eps, ww, K, nout, rr, out)
-  const bool rms = rms_w != nullptr;
-  switch (mode) {
-    case 0: if (rms) GEMV(0, true); else GEMV(0, false); break;
-    case 1: if (rms) GEMV(1, true); else GEMV(1, false); break;
-    case 2: if (rms) GEMV(2, true); else GEMV(2, false); break;
-    case 4: if (rms) GEMV(4, true); else GEMV(4, false); break;
-    default: return (int)hipErrorInvalidValue;
-  }
-#undef GEMV
-  return (int)hipGetLastError();
+  const bool known = with_mode_rms(mode, rms_w != nullptr, [&](auto M, auto R) {
+    hipLaunchKernelGGL((k_gemv<M(), R()>), g, b, 0, s, (const uint16_t*)x, rms_w, eps, (const uint16_t*)W, K, nout,
+                       (const uint16_t*)res, out);
+  });
+  return known ? (int)hipGetLastError() : (int)hipErrorInvalidValue;
 }
 
 // dec_gemv over Q4G32 weights (k_gemv_q4): Wq [N, K/2] nibbles, Wsm [N, K/32] bf16 (d, m) pairs.
 // K % 32 == 0, K <= 16384, 16-B aligned x / Wq, 4-B aligned Wsm.
-}  // extern "C"
-
-template <int BITS>
-static int gemv_qn(int mode, const void* x, const float* rms_w, float eps, const void* Wq, const void* Wsm, int N,
-                   int K, const void* res, void* out, hipStream_t s) {
-  if (K <= 0 || K % kQ4Group || K > kGemvQ4MaxK || N <= 0 || (mode == 2 && N % 32) || (mode == 1 && !res) ||
-      ((uintptr_t)Wq | (uintptr_t)x) % 16 || (uintptr_t)Wsm % 4 || (rms_w && (uintptr_t)rms_w % 16))
-    return (int)hipErrorInvalidValue;
-  // rows per wave: 4, or 8 with SPL_Q4_ROWS=8 (A/B knob: more bytes in flight per wave, half the blocks)
-  static const int R = [] {
-    const char* e = getenv("SPL_Q4_ROWS");
-    return e && atoi(e) == 8 ? 8 : 4;
-  }();
-  const int nout = mode == 2 ? N / 2 : N;
-  const int per_block = 4 * (mode == 2 ? R / 2 : R);
-  const dim3 g((unsigned)((nout + per_block - 1) / per_block)), b(256);
-  const size_t lds = (size_t)(K / kQ4Group) * kQ4Rec * sizeof(float);
-  const uint16_t *xx = (const uint16_t*)x, *rr = (const uint16_t*)res;
-  const uint8_t* wq = (const uint8_t*)Wq;
-  const uint32_t* wsm = (const uint32_t*)Wsm;
-#define GEMV(M_, R_)                                                                                           \
-  do {                                                                                                         \
-    if (R == 8) hipLaunchKernelGGL((k_gemv_q4<M_, R_, 8, BITS>), g, b, lds, s, xx, rms_w, eps, wq, wsm, K, nout, rr, out); \
-    else hipLaunchKernelGGL((k_gemv_q4<M_, R_, 4, BITS>), g, b, lds, s, xx, rms_w, eps, wq, wsm, K, nout, rr, out);      \
-  } while (0)
-  const bool rms = rms_w != nullptr;
-  switch (mode) {
-    case 0: if (rms) GEMV(0, true); else GEMV(0, false); break;
-    case 1: if (rms) GEMV(1, true); else GEMV(1, false); break;
-    case 2: if (rms) GEMV(2, true); else GEMV(2, false); break;
-    case 4: if (rms) GEMV(4, true); else GEMV(4, false); break;
-    default: return (int)hipErrorInvalidValue;
-  }
-#undef GEMV
-  return (int)hipGetLastError();
-}
-
-extern "C" {
-
 int dec_gemv_q4(int mode, const void* x, const float* rms_w, float eps, const void* Wq, const void* Wsm, int N,
                 int K, const void* res, void* out, hipStream_t s) {
   return gemv_qn<4>(mode, x, rms_w, eps, Wq, Wsm, N, K, res, out, s);
@@ -1954,40 +1824,31 @@ int dec_gemv_q8(int mode, const void* x, const float* rms_w, float eps, const vo
 
 // bf16 W [N, K] (row-major, contiguous) <-> Q8G32 planes
 int dec_q8_quantize(const void* W, long N, int K, void* Wq, void* Wsm, hipStream_t s) {
-  if (N <= 0 || K <= 0 || K % kQ4Group || ((uintptr_t)W | (uintptr_t)Wq) % 16 || (uintptr_t)Wsm % 4)
-    return (int)hipErrorInvalidValue;
-  const long groups = N * (K / kQ4Group);
-  hipLaunchKernelGGL(k_q8_quant, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, s, (const uint16_t*)W, groups,
-                     (uint8_t*)Wq, (uint32_t*)Wsm);
-  return (int)hipGetLastError();
+  return quant_launch(W, N, K, Wq, Wsm, [&](dim3 g, long groups) {
+    hipLaunchKernelGGL(k_q8_quant, g, dim3(256), 0, s, (const uint16_t*)W, groups, (uint8_t*)Wq, (uint32_t*)Wsm);
+  });
 }
 
 int dec_q8_dequant(const void* Wq, const void* Wsm, long N, int K, void* W, hipStream_t s) {
-  if (N <= 0 || K <= 0 || K % kQ4Group || ((uintptr_t)W | (uintptr_t)Wq) % 16 || (uintptr_t)Wsm % 4)
-    return (int)hipErrorInvalidValue;
-  const long groups = N * (K / kQ4Group);
-  hipLaunchKernelGGL(k_q8_dequant, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, s, (const uint8_t*)Wq,
-                     (const uint32_t*)Wsm, groups, (uint16_t*)W);
-  return (int)hipGetLastError();
+  return quant_launch(W, N, K, Wq, Wsm, [&](dim3 g, long groups) {
+    hipLaunchKernelGGL(k_q8_dequant, g, dim3(256), 0, s, (const uint8_t*)Wq, (const uint32_t*)Wsm, groups,
+                       (uint16_t*)W);
+  });
 }
 
 // bf16 W [N, K] (row-major, contiguous) <-> Q4G32 planes
 int dec_q4_quantize(const void* W, long N, int K, void* Wq, void* Wsm, hipStream_t s) {
-  if (N <= 0 || K <= 0 || K % kQ4Group || ((uintptr_t)W | (uintptr_t)Wq) % 16 || (uintptr_t)Wsm % 4)
-    return (int)hipErrorInvalidValue;
-  const long groups = N * (K / kQ4Group);
-  hipLaunchKernelGGL(k_q4_quant, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, s, (const uint16_t*)W, groups,
-                     K / kQ4Group, (uint8_t*)Wq, (uint32_t*)Wsm);
-  return (int)hipGetLastError();
+  return quant_launch(W, N, K, Wq, Wsm, [&](dim3 g, long groups) {
+    hipLaunchKernelGGL(k_q4_quant, g, dim3(256), 0, s, (const uint16_t*)W, groups, K / kQ4Group, (uint8_t*)Wq,
+                       (uint32_t*)Wsm);
+  });
 }
 
 int dec_q4_dequant(const void* Wq, const void* Wsm, long N, int K, void* W, hipStream_t s) {
-  if (N <= 0 || K <= 0 || K % kQ4Group || ((uintptr_t)W | (uintptr_t)Wq) % 16 || (uintptr_t)Wsm % 4)
-    return (int)hipErrorInvalidValue;
-  const long groups = N * (K / kQ4Group);
-  hipLaunchKernelGGL(k_q4_dequant, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, s, (const uint8_t*)Wq,
-                     (const uint32_t*)Wsm, groups, (uint16_t*)W);
-  return (int)hipGetLastError();
+  return quant_launch(W, N, K, Wq, Wsm, [&](dim3 g, long groups) {
+    hipLaunchKernelGGL(k_q4_dequant, g, dim3(256), 0, s, (const uint8_t*)Wq, (const uint32_t*)Wsm, groups,
+                       (uint16_t*)W);
+  });
 }
 
 int dec_embed_tok(const void* emb, int d, const int32_t* st, void* x, hipStream_t s) {
@@ -2009,13 +1870,13 @@ int dec_rope_kv(void* qkv, int H, int KVH, int hd, const float* cos_tab, const f
 // floats of the workspace dec_sample_ws needs
 long dec_sample_ws_floats() { return SB_FLOATS; }
 
-// dec_sample with a caller-owned workspace (dec_sample_ws_floats() floats): vocabularies past 4096
+// The sampler, with a caller-owned workspace (dec_sample_ws_floats() floats): vocabularies past 4096
 // tokens run the multi-block chain (k_sb_*), smaller ones the single-workgroup register sampler
 int dec_sample_ws(const float* logits, int V, const uint8_t* mask, float top_p, float temp, uint64_t seed,
                   int32_t* st, int inc_pos, int32_t* host_tok, float* ws, hipStream_t s) {
   if (V <= 0 || !ws) return (int)hipErrorInvalidValue;
-  if (V <= 4096) {
-    hipLaunchKernelGGL(k_sample_reg<4>, dim3(1), dim3(kSampThreads), 0, s, logits, V, mask, top_p, temp, seed, st,
+  if (V <= kSampThreads * kSampRegs) {
+    hipLaunchKernelGGL(k_sample_reg, dim3(1), dim3(kSampThreads), 0, s, logits, V, mask, top_p, temp, seed, st,
                        inc_pos, host_tok);
     return (int)hipGetLastError();
   }
@@ -2030,18 +1891,6 @@ int dec_sample_ws(const float* logits, int V, const uint8_t* mask, float top_p, 
   }
   hipLaunchKernelGGL(k_sb_part, g, b, 0, s, logits, V, mask, temp, nucleus, ws);
   hipLaunchKernelGGL(k_sb_draw, dim3(1), dim3(kSbBins), 0, s, logits, V, mask, temp, seed, ws, st, inc_pos, host_tok);
-  return (int)hipGetLastError();
-}
-
-int dec_sample(const float* logits, int V, const uint8_t* mask, float top_p, float temp, uint64_t seed, int32_t* st,
-               int inc_pos, int32_t* host_tok, hipStream_t s) {
-  if (V <= 0) return (int)hipErrorInvalidValue;
-  if (V <= kSampThreads * 32)  // registers hold the vocabulary (llama-2 / mistral: 32000)
-    hipLaunchKernelGGL(k_sample_reg<32>, dim3(1), dim3(kSampThreads), 0, s, logits, V, mask, top_p, temp, seed, st,
-                       inc_pos, host_tok);
-  else
-    hipLaunchKernelGGL(k_sample, dim3(1), dim3(kSampThreads), 0, s, logits, V, mask, top_p, temp, seed, st, inc_pos,
-                       host_tok);
   return (int)hipGetLastError();
 }
 

@@ -91,7 +91,7 @@ __global__ __launch_bounds__(256) void k_ln(const uint16_t* __restrict__ x, cons
 constexpr int HD = 64;  // head dim
 
 // ------------------------------------------- attention, 16x16 MFMA form --
-// k_attn2: the completion daemon's causal prefill (grouped heads) and the encoder's fallback form.
+// k_attn2: the encoder's fallback form (NOMIC_ATTN=6).
 // One workgroup = 128 query rows of one (sequence, head); 4 waves x 32 rows
 // (two 16-row q-blocks per wave).  "Swapped" products keep every per-query
 // quantity lane-local (guide §3 accumulator-as-operand, T10, T12):
@@ -139,10 +139,8 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // Score scaling and row sums are packed (v_pk_fma / v_pk_add), and the K/V source pointers are
 // advanced per tile instead of recomputed with 64-bit multiplies.
-// CAUSAL: query row i of a sequence sees keys 0..i (the completion daemon's prefill, K18); key
-// tiles past the block's last row are skipped, the diagonal tiles masked per score.  kv_heads <
-// heads: grouped-query attention, q head h reads kv head h / (heads / kv_heads); the qkv rows are
-// [q (heads) | k (kv_heads) | v (kv_heads)] x HD.
+// kv_heads < heads: grouped-query attention, q head h reads kv head h / (heads / kv_heads); the
+// qkv rows are [q (heads) | k (kv_heads) | v (kv_heads)] x HD.  The encoder passes kv_heads = heads.
 //
 // Measured and removed (each was a template parameter; 64 sequences x 512 tokens, TFLOP/s):
 //   - the 2-D grid without the XCD remap, shuffle (ds_bpermute) reductions with a scalar exp path
@@ -153,7 +151,11 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 //   - 8 waves over 256-row q-blocks (QW 8): 483 against 513 (profiles/r2_attn_8wave_ab.jsonl)
 //   - the next tile's K/V loads issued after the S^T MFMAs instead of before them (LATE): 539
 //     against 546, +-1 % on every form (profiles/r3_attn_late_load_ab.jsonl)
-template <bool CAUSAL>
+//   - the CAUSAL arm behind dec_attn_prefill (key tiles past the block's last row skipped, diagonal
+//     tiles masked per score; head dim 64, fresh prompts only).  Only a test called it: the
+//     completion daemon prefills through dec_attn_prefill_kv (decoder_kernels.hip), which also
+//     continues a live cache.  The two were never timed against each other
+//     (profiles/decoder_prune/README.md)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1))) void k_attn2(
     const uint16_t* __restrict__ qkv, uint16_t* __restrict__ out,
                                                const int32_t* __restrict__ cu, const int32_t* __restrict__ qblocks,
@@ -221,8 +223,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1))) void k
     }
   };
 
-  int ntiles = (int)((len + KT - 1) / KT);
-  if constexpr (CAUSAL) ntiles = min(ntiles, (int)((qstart + 128 + KT - 1) / KT));
+  const int ntiles = (int)((len + KT - 1) / KT);
   gload(0);
   lwrite(0);
   __syncthreads();
@@ -259,16 +260,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1))) void k
     const bool full = k0 + KT <= len;
 #pragma unroll
     for (int qb = 0; qb < 2; ++qb) {
-      if constexpr (CAUSAL) {
-        if (k0 + KT - 1 > qstart) {  // a diagonal tile: keys after the query are masked
-          const long qrow = qstart + wave * 32 + qb * 16 + li;
-#pragma unroll
-          for (int kb = 0; kb < KT / 16; ++kb)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-              if (k0 + kb * 16 + 4 * g + r > qrow) s[kb][qb][r] = -1e30f;
-        }
-      }
       if (!full) {
 #pragma unroll
         for (int kb = 0; kb < KT / 16; ++kb)
@@ -785,22 +776,11 @@ int nomic_attention(const void* qkv, void* out, const int32_t* cu, const int32_t
   if (heads * HD * 3 % 8) return (int)hipErrorInvalidValue;
   const float scale_log2 = scale * 1.4426950408889634f;
   if (g_attn_variant == 6)
-    hipLaunchKernelGGL(k_attn2<false>, dim3(nqb * heads), dim3(256), 0, s, (const uint16_t*)qkv,
+    hipLaunchKernelGGL(k_attn2, dim3(nqb * heads), dim3(256), 0, s, (const uint16_t*)qkv,
                        (uint16_t*)out, cu, qblocks, heads, scale_log2, heads);
   else
     hipLaunchKernelGGL(k_attn3<>, dim3(nqb * heads), dim3(256), 0, s, (const uint16_t*)qkv, (uint16_t*)out, cu,
                        qblocks, heads, scale_log2);
-  return (int)hipGetLastError();
-}
-
-// causal (prefill) attention of the completion daemon's decoder: qkv rows [q (heads) | k | v
-// (kv_heads each)] x 64, out [T, heads * 64]; 128-row q-blocks as nomic_attention
-int dec_attn_prefill(const void* qkv, void* out, const int32_t* cu, const int32_t* qblocks, int nqb, int heads,
-                     int kv_heads, float scale, hipStream_t s) {
-  if (nqb <= 0) return 0;
-  if (kv_heads <= 0 || heads % kv_heads || (heads + 2 * kv_heads) * HD % 8) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_attn2<true>, dim3(nqb * heads), dim3(256), 0, s, (const uint16_t*)qkv,
-                     (uint16_t*)out, cu, qblocks, heads, scale * 1.4426950408889634f, kv_heads);
   return (int)hipGetLastError();
 }
 

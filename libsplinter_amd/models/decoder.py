@@ -15,7 +15,7 @@ the MI355X replacement, demo-grade as SURVEY §2.1 N8 scopes it:
   HIP kernels of ``csrc/hip/decoder_kernels.hip``, and so is the per-token
   decode attention over the KV cache (``dec_attn_decode``), the causal prefill
   attention of a fresh or continued prompt over the cache (``dec_attn_prefill_kv``,
-  head dim 64 / 128) and the nucleus sampler (``dec_sample``);
+  head dim 64 / 128) and the nucleus sampler (``dec_sample_ws``);
 * tokenizer: the GGUF's own -- SentencePiece score merging (model "llama") or
   byte-level BPE over the merges (model "gpt2"), models/llm_tokenizer.py -- or,
   for random init, bytes 0..255 + BOS/EOS.
@@ -122,18 +122,21 @@ class Q4Weight:
     at a time into a bf16 scratch for the MFMA GEMM.  The role of llama.cpp's Q4 weights in the
     reference's llama_decode (splainference.cpp:272-330)."""
 
+    bits = 4  # Q8Weight: 8; picks the dec_q<bits>_* symbols and the bytes per row, K * bits / 8
+
     def __init__(self, q: torch.Tensor, sm: torch.Tensor):
         self.q, self.sm = q, sm
-        self.shape = (q.shape[0], q.shape[1] * 2)
+        self.shape = (q.shape[0], q.shape[1] * 8 // self.bits)
 
     @classmethod
-    def quantize(cls, L, w: torch.Tensor) -> "Q4Weight":
+    def quantize(cls, L, w: torch.Tensor):
         from .nomic import _chk, _stream
         w = w.to(torch.bfloat16).contiguous()
         N, K = w.shape
-        q = torch.empty((N, K // 2), dtype=torch.uint8, device=w.device)
+        q = torch.empty((N, K * cls.bits // 8), dtype=torch.uint8, device=w.device)
         sm = torch.empty((N, K // 32), dtype=torch.int32, device=w.device)
-        _chk(L.dec_q4_quantize(w.data_ptr(), N, K, q.data_ptr(), sm.data_ptr(), _stream()), "q4_quantize")
+        name = f"dec_q{cls.bits}_quantize"
+        _chk(getattr(L, name)(w.data_ptr(), N, K, q.data_ptr(), sm.data_ptr(), _stream()), name[4:])
         return cls(q, sm)
 
     def dequant(self, L, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -141,13 +144,12 @@ class Q4Weight:
         N, K = self.shape
         if out is None:
             out = torch.empty((N, K), dtype=torch.bfloat16, device=self.q.device)
-        _chk(L.dec_q4_dequant(self.q.data_ptr(), self.sm.data_ptr(), N, K, out.data_ptr(), _stream()), "q4_dequant")
+        name = f"dec_q{self.bits}_dequant"
+        _chk(getattr(L, name)(self.q.data_ptr(), self.sm.data_ptr(), N, K, out.data_ptr(), _stream()), name[4:])
         return out
 
     def nbytes(self) -> int:
         return self.q.numel() + self.sm.numel() * 4
-
-    bits = 4
 
 
 class Q8Weight(Q4Weight):
@@ -156,28 +158,6 @@ class Q8Weight(Q4Weight):
     bits (a Q4_K_M file's Q6_K attn_v / ffn_down / output), so they are not re-gridded below the
     file's precision.  Decode reads it with dec_gemv_q8, prefill dequantises with dec_q8_dequant."""
     bits = 8
-
-    def __init__(self, q: torch.Tensor, sm: torch.Tensor):
-        self.q, self.sm = q, sm
-        self.shape = (q.shape[0], q.shape[1])
-
-    @classmethod
-    def quantize(cls, L, w: torch.Tensor) -> "Q8Weight":
-        from .nomic import _chk, _stream
-        w = w.to(torch.bfloat16).contiguous()
-        N, K = w.shape
-        q = torch.empty((N, K), dtype=torch.uint8, device=w.device)
-        sm = torch.empty((N, K // 32), dtype=torch.int32, device=w.device)
-        _chk(L.dec_q8_quantize(w.data_ptr(), N, K, q.data_ptr(), sm.data_ptr(), _stream()), "q8_quantize")
-        return cls(q, sm)
-
-    def dequant(self, L, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        from .nomic import _chk, _stream
-        N, K = self.shape
-        if out is None:
-            out = torch.empty((N, K), dtype=torch.bfloat16, device=self.q.device)
-        _chk(L.dec_q8_dequant(self.q.data_ptr(), self.sm.data_ptr(), N, K, out.data_ptr(), _stream()), "q8_dequant")
-        return out
 
 
 # GGUF tensor types stored at <= 4 bits per weight (Q4_0, Q4_1, Q2_K, Q3_K, Q4_K, IQ2/IQ3/IQ4, IQ1):
@@ -270,8 +250,6 @@ class CausalLM:
             self.L.dec_attn_decode_st.restype = c_int
             self.L.dec_attn_decode_ws.argtypes = [P, P, P, c_long, c_int, c_int, c_int, c_int, c_float, P, P, P, P]
             self.L.dec_attn_decode_ws.restype = c_int
-            self.L.dec_attn_prefill.argtypes = [P, P, P, P, c_int, c_int, c_int, c_float, P]
-            self.L.dec_attn_prefill.restype = c_int
             self.L.dec_attn_prefill_kv.argtypes = [P, c_long, P, P, c_long, c_int, c_int, c_int, c_int, c_int, c_float,
                                                    P, c_long, P]
             self.L.dec_attn_prefill_kv.restype = c_int
@@ -281,8 +259,6 @@ class CausalLM:
             self.L.dec_embed_tok.restype = c_int
             self.L.dec_rope_kv.argtypes = [P, c_int, c_int, c_int, P, P, P, P, P, c_long, P]
             self.L.dec_rope_kv.restype = c_int
-            self.L.dec_sample.argtypes = [P, c_int, P, c_float, c_float, ctypes.c_uint64, P, c_int, P, P]
-            self.L.dec_sample.restype = c_int
             self.L.dec_sample_ws.argtypes = [P, c_int, P, c_float, c_float, ctypes.c_uint64, P, c_int, P, P, P]
             self.L.dec_sample_ws.restype = c_int
             self.L.dec_sample_ws_floats.argtypes = []
@@ -455,7 +431,7 @@ class DecodeEngine:
     and the causal MFMA attention, then per token ONE replay of a HIP graph holding the whole
     decode step -- embedding row, per layer (RMSNorm+QKV GEMV, RoPE + KV-cache append, decode
     attention, o GEMV + residual, RMSNorm+up|gate GEMV + SwiGLU, down GEMV + residual), final
-    RMSNorm + LM-head GEMV and the top-p / temperature sampler (dec_sample).  Every kernel reads
+    RMSNorm + LM-head GEMV and the top-p / temperature sampler (dec_sample_ws).  Every kernel reads
     the position and the input token from a device state {pos, token, step}, so the captured
     arguments never change; the host reads back only the sampled token id (pinned memory).
     Reference: splainference.cpp:272-365 (sampler chain, llama_decode per token)."""

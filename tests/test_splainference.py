@@ -103,12 +103,14 @@ def test_decoder_rmsnorm_rope_kernels_vs_fp32():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("hd,H,KVH", [(128, 32, 8), (64, 8, 8), (128, 16, 2), (256, 8, 1), (64, 16, 8), (192, 8, 4)])
+@pytest.mark.parametrize("hd,H,KVH", [(128, 32, 8), (64, 8, 8), (128, 16, 2), (256, 8, 1), (64, 16, 8), (192, 8, 4),
+                                      (128, 12, 4)])
 def test_decoder_attn_decode_kernel_vs_fp32(hd, H, KVH):
     """dec_attn_decode (csrc/hip/decoder_kernels.hip) against an fp32 softmax(q k^T) v reference,
     cache lengths on both sides of the 64-key chunk and 256-key workgroup boundaries; past 512 keys
     the split-L (flash-decoding) kernels + combine, also driven by the device-side length with a
-    larger capacity (empty splits)."""
+    larger capacity (empty splits).  12 heads over 4 KV heads is a query-group size of 3, which has no
+    grouped kernel: k_attn_decode<2> up to 512 keys, k_attn_decode_split<2, 1> beyond."""
     import torch
     from libsplinter_amd.models.decoder import CausalLM, DecoderConfig
     m = CausalLM.random(DecoderConfig(layers=1), seed=1, device="cuda")
@@ -158,7 +160,8 @@ def test_decoder_kv_cache_matches_full_recompute_cpu():
 @pytest.mark.gpu
 @pytest.mark.parametrize("H,KVH,n", [(8, 8, 300), (8, 2, 129), (12, 4, 64)])
 def test_decoder_prefill_attention_causal_vs_fp32(H, KVH, n):
-    """dec_attn_prefill (k_attn2<CAUSAL>, grouped-query) against fp32 causal softmax(q k^T) v."""
+    """dec_attn_prefill_kv (k_prefill_attn<64>, grouped-query) on a fresh prompt (pos0 = 0), the cache
+    holding the K / V columns of the prompt's own qkv rows, against fp32 causal softmax(q k^T) v."""
     import torch
     from libsplinter_amd.models.decoder import CausalLM, DecoderConfig
     m = CausalLM.random(DecoderConfig(layers=1), seed=1, device="cuda")
@@ -166,10 +169,11 @@ def test_decoder_prefill_attention_causal_vs_fp32(H, KVH, n):
     g = torch.Generator(device="cuda").manual_seed(5)
     qkv = torch.randn((n, (H + 2 * KVH) * hd), device="cuda", generator=g).to(torch.bfloat16)
     out = torch.full((n, H * hd), float("nan"), device="cuda").to(torch.bfloat16)
-    cu = torch.tensor([0, n], dtype=torch.int32, device="cuda")
-    qb = torch.tensor([v for q0 in range(0, n, 128) for v in (0, q0)], dtype=torch.int32, device="cuda")
-    assert m.L.dec_attn_prefill(qkv.data_ptr(), out.data_ptr(), cu.data_ptr(), qb.data_ptr(), qb.numel() // 2, H, KVH,
-                                hd ** -0.5, None) == 0
+    ld = (H + 2 * KVH) * hd
+    kc = qkv[:, H * hd:(H + KVH) * hd].contiguous()
+    vc = qkv[:, (H + KVH) * hd:].contiguous()
+    assert m.L.dec_attn_prefill_kv(qkv.data_ptr(), ld, kc.data_ptr(), vc.data_ptr(), KVH * hd, n, 0, H, KVH, hd,
+                                   hd ** -0.5, out.data_ptr(), H * hd, None) == 0
     torch.cuda.synchronize()
     q = qkv[:, : H * hd].float().reshape(n, H, hd)
     k = qkv[:, H * hd:(H + KVH) * hd].float().reshape(n, KVH, hd).repeat_interleave(H // KVH, 1)
@@ -448,26 +452,32 @@ def test_decode_engine_q4_matches_eager_and_bf16():
 
 
 @pytest.mark.gpu
-def test_dec_sample_nucleus_temperature_distribution():
-    """dec_sample: greedy at tiny temperature, never outside the top-p nucleus, and draw
-    frequencies that follow the renormalised tempered nucleus distribution."""
+@pytest.mark.parametrize("V", [384, 4096])
+def test_dec_sample_nucleus_temperature_distribution(V):
+    """dec_sample_ws up to 4096 tokens (k_sample_reg, the single-workgroup register sampler): greedy
+    at tiny temperature, never outside the top-p nucleus, and draw frequencies that follow the
+    renormalised tempered nucleus distribution.  4096 is the last vocabulary on this kernel; there
+    the most probable token sits at the last index, in the last register of the last thread."""
     import torch
     from libsplinter_amd.models.decoder import CausalLM, DecoderConfig
     m = CausalLM.random(DecoderConfig(layers=1), seed=1, device="cuda")
-    V = 384
     p = torch.tensor([0.4, 0.25, 0.15, 0.08, 0.05] + [0.07 / (V - 5)] * (V - 5), dtype=torch.float64)
     perm = torch.randperm(V, generator=torch.Generator().manual_seed(3))
+    if V == 4096:
+        j = int((perm == V - 1).nonzero())
+        perm[0], perm[j] = perm[j].clone(), perm[0].clone()
     logits = torch.empty(V, dtype=torch.float64)
     logits[perm] = p.log()
     lg = logits.float().cuda()
     st = torch.zeros(4, dtype=torch.int32, device="cuda")
     host = torch.zeros(1, dtype=torch.int32, pin_memory=True)
+    ws = torch.empty(m.L.dec_sample_ws_floats(), dtype=torch.float32, device="cuda")
 
     def draw(top_p, temp, n):
         out = []
         for _ in range(n):
-            assert m.L.dec_sample(lg.data_ptr(), V, None, top_p, temp, 1234, st.data_ptr(), 0, host.data_ptr(),
-                                  None) == 0
+            assert m.L.dec_sample_ws(lg.data_ptr(), V, None, top_p, temp, 1234, st.data_ptr(), 0, host.data_ptr(),
+                                     ws.data_ptr(), None) == 0
             torch.cuda.synchronize()
             out.append(int(host[0]))
         return out
@@ -485,9 +495,10 @@ def test_dec_sample_nucleus_temperature_distribution():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("V", [50000, 128256])
+@pytest.mark.parametrize("V", [4097, 50000, 128256])
 def test_dec_sample_multiblock_distribution(V):
-    """dec_sample_ws past 4096 tokens (the 64-block k_sb_* chain): greedy at tiny temperature,
+    """dec_sample_ws past 4096 tokens (the 64-block k_sb_* chain; 4097 is the first vocabulary on it,
+    in slices of 65 tokens): greedy at tiny temperature,
     never outside the top-p nucleus, tempered nucleus frequencies, with the top tokens scattered
     over different blocks; top_p = 1 keeps every token eligible."""
     import torch
