@@ -1,0 +1,119 @@
+// decoder_common.hpp — helpers shared by decoder_kernels.hip (one generation) and decoder_batch.hip
+// (up to 16 generations per step): bf16 packing, wave reductions, the device state record, the
+// sampler's workspace layout and draw, and the split-L geometry of the decode attention.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstdint>
+#include <cmath>
+#include <cstdlib>
+
+namespace {
+
+typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ float bf2f(uint32_t h16) { return __uint_as_float(h16 << 16); }
+__device__ __forceinline__ uint32_t pk2(float a, float b) {
+  const bf16x2_t v = {(__bf16)a, (__bf16)b};
+  return __builtin_bit_cast(uint32_t, v);
+}
+__device__ __forceinline__ void unpack8(uint4 v, float* f) {
+  f[0] = bf2f(v.x & 0xffff); f[1] = bf2f(v.x >> 16);
+  f[2] = bf2f(v.y & 0xffff); f[3] = bf2f(v.y >> 16);
+  f[4] = bf2f(v.z & 0xffff); f[5] = bf2f(v.z >> 16);
+  f[6] = bf2f(v.w & 0xffff); f[7] = bf2f(v.w >> 16);
+}
+__device__ __forceinline__ uint4 pack8(const float* f) {
+  return make_uint4(pk2(f[0], f[1]), pk2(f[2], f[3]), pk2(f[4], f[5]), pk2(f[6], f[7]));
+}
+
+// Device state of a generation (int32): [0] pos = tokens already in the KV cache, [1] token = the
+// token the next step consumes (the last sampled one), [2] step = sampler draws so far.  The batched
+// step (decoder_batch.hip) keeps one 8-word record per sequence slot: the same three words, then
+// [3] active (0 / 1), [4] [5] the slot's sampler seed (low, high half), [6] [7] reserved (zero).
+enum { ST_POS = 0, ST_TOK = 1, ST_STEP = 2, ST_ACTIVE = 3, ST_SEED_LO = 4, ST_SEED_HI = 5, ST_WORDS = 8 };
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+// decode attention geometry: waves of the walking kernels, the single-workgroup key limit of the
+// grouped kernel, and the flash-decoding split limits
+constexpr int kDecWaves = 16;
+constexpr int kSmallL = 512;
+constexpr int kSplitWaves = 4;
+constexpr int kMaxSplits = 32;
+
+// splits for a cache of (up to) L keys: the single-workgroup kernel up to 512 keys, then one split per
+// 256 keys, at most kMaxSplits (sweep over 4..32 splits at H 32 / KVH 8 / hd 128:
+// profiles/r2_decode_splits.jsonl)
+inline int decode_splits(int L) {
+  static const int env = [] {
+    const char* e = getenv("SPL_DEC_SPLITS");
+    return e && *e ? atoi(e) : -1;
+  }();
+  if (env >= 1) return env < kMaxSplits ? env : kMaxSplits;
+  if (L <= 512) return 1;
+  const int sp = (L + 255) / 256;
+  return sp > kMaxSplits ? kMaxSplits : sp;
+}
+
+// counter-based uniform in [0, 1): splitmix64 of (seed, draw index)
+__device__ __forceinline__ double uniform01(uint64_t seed, uint64_t n) {
+  uint64_t z = seed + (n + 1) * 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  z ^= z >> 31;
+  return (double)(z >> 11) * (1.0 / 9007199254740992.0);
+}
+
+constexpr int kSampThreads = 1024;
+constexpr int kSampRegs = 4;  // logits per thread: vocabularies up to 4096 tokens, longer ones run k_sb_*
+
+__device__ float block_reduce(float v, float* sh, bool is_max) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  v = is_max ? wave_max(v) : wave_sum(v);
+  __syncthreads();
+  if (lane == 0) sh[wave] = v;
+  __syncthreads();
+  float r = sh[0];
+  for (int w = 1; w < kSampThreads / 64; ++w) r = is_max ? fmaxf(r, sh[w]) : r + sh[w];
+  return r;
+}
+
+// The multi-block sampler's workspace layout (floats, caller-owned so the chain can be graph-captured)
+constexpr int kSbBlocks = 64, kSbThreads = 256, kSbBins = 1024;
+enum {
+  SB_BMAX = 0,                          // [64] block max
+  SB_BIDX = SB_BMAX + kSbBlocks,        // [64] first index of the block max (as int bits)
+  SB_BZ = SB_BIDX + kSbBlocks,          // [64] block mass sum exp(l - M)
+  SB_BPART = SB_BZ + kSbBlocks,         // [64] block kept mass (tempered)
+  SB_SCAL = SB_BPART + kSbBlocks,       // [8]  M, Z, lo, w, above, cut
+  SB_HIST = SB_SCAL + 8,                // [64][1024] per-block histograms
+  SB_FLOATS = SB_HIST + kSbBlocks * kSbBins
+};
+
+__device__ __forceinline__ float sb_logit(const float* logits, const uint8_t* mask, int i) {
+  return (mask && !mask[i]) ? -INFINITY : logits[i];
+}
+
+template <int NT>
+__device__ float sb_reduce(float v, bool is_max) {
+  __shared__ float sh[NT / 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  v = is_max ? wave_max(v) : wave_sum(v);
+  __syncthreads();
+  if (lane == 0) sh[wave] = v;
+  __syncthreads();
+  float r = sh[0];
+  for (int w = 1; w < NT / 64; ++w) r = is_max ? fmaxf(r, sh[w]) : r + sh[w];
+  return r;
+}
+
+}  // namespace

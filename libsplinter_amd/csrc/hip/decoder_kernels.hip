@@ -10,7 +10,7 @@
 //
 //   dec_gemv      M = 1 projections of the decode step (optionally with the RMSNorm of x
 //                 fused in): weight rows streamed once with 16-B loads, 4 rows per wave in flight
-//   dec_embed_tok / dec_rope_kv / dec_sample_ws
+//   dec_embed_tok / dec_rope_kv / dec_sample_ws   (their forms over up to 16 sequence slots: decoder_batch.hip)
 //                 the rest of a decode step, driven by a device-resident state {pos, token,
 //                 step} so a whole step (all layers + sampling) can be captured once in a HIP
 //                 graph and replayed per token with no host arguments changing
@@ -26,24 +26,9 @@
 #include <mutex>
 #include <type_traits>
 
+#include "decoder_common.hpp"
+
 namespace {
-
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float bf2f(uint32_t h16) { return __uint_as_float(h16 << 16); }
-__device__ __forceinline__ uint32_t pk2(float a, float b) {
-  const bf16x2_t v = {(__bf16)a, (__bf16)b};
-  return __builtin_bit_cast(uint32_t, v);
-}
-__device__ __forceinline__ void unpack8(uint4 v, float* f) {
-  f[0] = bf2f(v.x & 0xffff); f[1] = bf2f(v.x >> 16);
-  f[2] = bf2f(v.y & 0xffff); f[3] = bf2f(v.y >> 16);
-  f[4] = bf2f(v.z & 0xffff); f[5] = bf2f(v.z >> 16);
-  f[6] = bf2f(v.w & 0xffff); f[7] = bf2f(v.w >> 16);
-}
-__device__ __forceinline__ uint4 pack8(const float* f) {
-  return make_uint4(pk2(f[0], f[1]), pk2(f[2], f[3]), pk2(f[4], f[5]), pk2(f[6], f[7]));
-}
 
 // One wave per row, 4 rows per 256-thread block.  Rows of up to 64 x 8 x 4 =
 // 2048 elements stay in registers (single HBM read); wider rows re-read their
@@ -137,8 +122,6 @@ __global__ __launch_bounds__(256) void k_rope(uint16_t* __restrict__ qkv, long l
 // are accumulated with p broadcast by __shfl, each lane owning DPL = hd/64 contiguous
 // output dims.  The 16 partial (m, l, acc) states merge in LDS.  K/V are [L, ldkv] rows
 // (ldkv = KVH*hd elements) starting at the kv head's column.
-constexpr int kDecWaves = 16;
-
 template <int DPL>
 __global__ __launch_bounds__(kDecWaves * 64) void k_attn_decode(const uint16_t* __restrict__ q, const uint16_t* __restrict__ K,
                                                      const uint16_t* __restrict__ V, long ldkv, int L, int grp,
@@ -237,7 +220,6 @@ __global__ __launch_bounds__(kDecWaves * 64) void k_attn_decode(const uint16_t* 
 // (one load round per phase, shuffle + LDS reduction) measured slower: 14.1 us (r3_decode_attn_small_wide_ab.jsonl).
 // Its split form runs the flash-decoding splits of longer caches: 3000-token prompt 0.840 -> 0.672 ms/token at 4 bits
 // (profiles/r3_decode_attn_grouped_split_ab.jsonl).
-constexpr int kSmallL = 512;
 // SPLIT: the same kernel as one split of the flash-decoding form -- workgroup (kvh, j) takes keys
 // [j * chunk, (j + 1) * chunk) (chunk <= kSmallL, the k_attn_decode_split geometry) and writes each head's
 // partial (max, sum, unnormalised P V) to ws for k_attn_combine.
@@ -386,9 +368,6 @@ __global__ __launch_bounds__(256) void k_attn_decode_g(const uint16_t* __restric
 // The chunk walk is k_attn_decode's, written out again on purpose: moved into one inlined function,
 // even word for word, it allocates other registers in 8 of the 20 kernels
 // (profiles/decoder_prune/README.md).
-constexpr int kSplitWaves = 4;
-constexpr int kMaxSplits = 32;
-
 template <int DPL, int G>
 __global__ __launch_bounds__(kSplitWaves * 64) void k_attn_decode_split(
     const uint16_t* __restrict__ q, const uint16_t* __restrict__ K, const uint16_t* __restrict__ V, long ldkv, int L,
@@ -522,20 +501,7 @@ __global__ void k_attn_combine(const float* __restrict__ ws, int S, int hd, uint
 }
 
 // ------------------------------------------------------------------ decode step --
-// Device state of a generation (int32): [0] pos = tokens already in the KV cache, [1] token = the
-// token the next step consumes (the last sampled one), [2] step = sampler draws so far.
-enum { ST_POS = 0, ST_TOK = 1, ST_STEP = 2 };
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
+// The device state record {pos, token, step} and the wave reductions: decoder_common.hpp.
 
 // y[n] = x . W[n, :] for one token.  x (bf16 [K], optionally RMS-normalised in LDS first: the
 // dec_rmsnorm + GEMV pair of a layer in one launch) is staged in LDS; each wave owns 4 weight rows
@@ -969,34 +935,11 @@ __global__ void k_rope_kv(uint16_t* __restrict__ qkv, int H, int KVH, int hd, co
   }
 }
 
-// counter-based uniform in [0, 1): splitmix64 of (seed, draw index)
-__device__ __forceinline__ double uniform01(uint64_t seed, uint64_t n) {
-  uint64_t z = seed + (n + 1) * 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return (double)(z >> 11) * (1.0 / 9007199254740992.0);
-}
-
 // top-p -> temperature -> categorical draw on the device (the reference's llama sampler chain,
 // splainference.cpp:272-279): the nucleus is the smallest set of the most probable tokens whose
 // probability reaches top_p, found as a logit threshold (no sort); the kept logits are divided by
 // temp and one token is drawn by an inclusive scan over the threads' masses.  Writes state.token
 // (and pos += inc_pos, step += 1) and the token to `host_tok` (pinned, may be null).
-constexpr int kSampThreads = 1024;
-constexpr int kSampRegs = 4;  // logits per thread: vocabularies up to 4096 tokens, longer ones run k_sb_*
-
-__device__ float block_reduce(float v, float* sh, bool is_max) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  v = is_max ? wave_max(v) : wave_sum(v);
-  __syncthreads();
-  if (lane == 0) sh[wave] = v;
-  __syncthreads();
-  float r = sh[0];
-  for (int w = 1; w < kSampThreads / 64; ++w) r = is_max ? fmaxf(r, sh[w]) : r + sh[w];
-  return r;
-}
-
 // One 1024-thread workgroup with the vocabulary held in registers (V <= 1024 * kSampRegs): thread t
 // owns tokens t + 1024 k and every pass reads them from VGPRs; the categorical draw walks the
 // threads' masses in that fixed order, an equally valid order of the same distribution.
@@ -1125,34 +1068,8 @@ __global__ __launch_bounds__(kSampThreads) void k_sample_reg(const float* __rest
 // ------------------------------------------------------------------ multi-block sampler --
 // The same sampler spread over kSbBlocks workgroups (one contiguous vocabulary slice each), as a
 // chain of small kernels: a single workgroup is bound by one CU (61 us at V 32000, 255-275 us at
-// V 128256).  Workspace layout (floats, caller-owned so the chain can be graph-captured):
-constexpr int kSbBlocks = 64, kSbThreads = 256, kSbBins = 1024;
-enum {
-  SB_BMAX = 0,                          // [64] block max
-  SB_BIDX = SB_BMAX + kSbBlocks,        // [64] first index of the block max (as int bits)
-  SB_BZ = SB_BIDX + kSbBlocks,          // [64] block mass sum exp(l - M)
-  SB_BPART = SB_BZ + kSbBlocks,         // [64] block kept mass (tempered)
-  SB_SCAL = SB_BPART + kSbBlocks,       // [8]  M, Z, lo, w, above, cut
-  SB_HIST = SB_SCAL + 8,                // [64][1024] per-block histograms
-  SB_FLOATS = SB_HIST + kSbBlocks * kSbBins
-};
-
-__device__ __forceinline__ float sb_logit(const float* logits, const uint8_t* mask, int i) {
-  return (mask && !mask[i]) ? -INFINITY : logits[i];
-}
-
-template <int NT>
-__device__ float sb_reduce(float v, bool is_max) {
-  __shared__ float sh[NT / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  v = is_max ? wave_max(v) : wave_sum(v);
-  __syncthreads();
-  if (lane == 0) sh[wave] = v;
-  __syncthreads();
-  float r = sh[0];
-  for (int w = 1; w < NT / 64; ++w) r = is_max ? fmaxf(r, sh[w]) : r + sh[w];
-  return r;
-}
+// V 128256).  The workspace (floats, caller-owned so the chain can be graph-captured) is laid out in
+// decoder_common.hpp.
 
 // A: block max and its first index
 __global__ __launch_bounds__(kSbThreads) void k_sb_max(const float* __restrict__ logits, int V,
@@ -1662,20 +1579,6 @@ float* split_workspace(hipStream_t s) {
   float* w = nullptr;
   if (hipMalloc((void**)&w, (size_t)128 * kMaxSplits * (256 + 2) * sizeof(float)) != hipSuccess) return nullptr;
   return table[s] = w;
-}
-
-// splits for a cache of (up to) L keys: the single-workgroup kernel up to 512 keys, then one split per
-// 256 keys, at most kMaxSplits (sweep over 4..32 splits at H 32 / KVH 8 / hd 128:
-// profiles/r2_decode_splits.jsonl)
-int decode_splits(int L) {
-  static const int env = [] {
-    const char* e = getenv("SPL_DEC_SPLITS");
-    return e && *e ? atoi(e) : -1;
-  }();
-  if (env >= 1) return env < kMaxSplits ? env : kMaxSplits;
-  if (L <= 512) return 1;
-  const int sp = (L + 255) / 256;
-  return sp > kMaxSplits ? kMaxSplits : sp;
 }
 
 }  // namespace

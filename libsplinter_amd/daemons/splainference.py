@@ -20,7 +20,8 @@ Contract kept from the reference daemon (/root/reference/splainference.cpp):
           chatter (:94-100), cold-start sweep of WAITING keys (:542-551), then
           poll the signal group every 50 ms (:570-592)
 Extra flags: --random-init (no GGUF: random llama weights, byte vocabulary,
-printable-byte sampling), --max-tokens (cap per request), --seed.
+printable-byte sampling), --max-tokens (cap per request), --seed, --batch N
+(GPU: up to N requests decoded together, one shared step per token; default 1).
 """
 from __future__ import annotations
 
@@ -98,13 +99,69 @@ def is_word_boundary(piece: bytes) -> bool:
     return bool(piece) and (piece[:1] in (b" ", b"\n") or b"\n" in piece)
 
 
+class CompletionStream:
+    """The streaming state of one request: tokens become pieces, pieces gather in a chunk, the chunk is
+    appended to the slot at a word boundary or every TOKEN_FLUSH_MAX tokens, truncated when the slot is full,
+    with the shard re-bid cadence (reference :332-364).  ``take`` a sampled token, produce the next one, then
+    ``flush_if_due``; ``close`` writes what is left."""
+
+    def __init__(self, store, tok, key: str, written: int, budget: int):
+        self.store, self.tok, self.key = store, tok, key
+        self.written, self.left = written, budget
+        self.chunk, self.run, self.rebid, self.oom, self.piece = b"", 0, 0, False, b""
+
+    def take(self, t: int) -> bool:
+        """False: the completion is over (token budget, or EOS / EOT / end-of-turn: llama_vocab_is_eog,
+        reference :310)."""
+        if self.left <= 0 or self.tok.is_eog(t):
+            return False
+        self.left -= 1
+        self.piece = self.tok.piece(t)
+        self.chunk += self.piece
+        self.run += 1
+        return True
+
+    def flush_if_due(self) -> bool:
+        """False: the slot is full and the completion was truncated."""
+        s, key = self.store, self.key
+        if (is_word_boundary(self.piece) or self.run >= TOKEN_FLUSH_MAX) and self.chunk:
+            if self.written + len(self.chunk) > s.max_val:
+                debug_post(s, f"[splainference][WARN]: Slot full, truncating completion: {key}")
+                if s.max_val - self.written > 0:
+                    s.append(key, self.chunk[: s.max_val - self.written])
+                self.oom = True
+                return False
+            self.written = s.append(key, self.chunk)
+            self.chunk, self.run = b"", 0
+            self.rebid += TOKEN_FLUSH_MAX
+            if self.rebid >= SHARD_REBID_TOKENS:
+                s.shard_rebid(SHARD_ID, INTENT_WILLNEED, SHARD_PRIO_LIVE, SHARD_DUR_LIVE)
+                self.rebid = 0
+        return True
+
+    def close(self) -> None:
+        s = self.store
+        if self.chunk and not self.oom and s.max_val - self.written > 0:
+            s.append(self.key, self.chunk[: s.max_val - self.written])
+
+
 class Splainference:
-    def __init__(self, store, model, tokenizer, sampler, system_prompt_key=None, max_tokens: int = 256):
+    def __init__(self, store, model, tokenizer, sampler, system_prompt_key=None, max_tokens: int = 256,
+                 batch: int = 1):
         self.store, self.model, self.tok, self.sampler = store, model, tokenizer, sampler
         self.system_prompt_key = system_prompt_key
         self.max_tokens = max_tokens
         self.engine = None
-        if getattr(model, "hip", False) and getattr(model, "decode_kernel", True):
+        self.batch_engine = None
+        gpu = getattr(model, "hip", False) and getattr(model, "decode_kernel", True)
+        if batch > 1 and not gpu:
+            print(f"[Warn]: --batch {batch} needs the GPU decode kernels; serving one request at a time.", flush=True)
+            batch = 1
+        if gpu and batch > 1:
+            from ..models.decoder import BatchDecodeEngine
+            self.batch_engine = BatchDecodeEngine(model, batch, sampler.top_p, sampler.temp, sampler.seed,
+                                                  sampler.mask)
+        elif gpu:
             from ..models.decoder import DecodeEngine
             self.engine = DecodeEngine(model, sampler.top_p, sampler.temp, sampler.seed, sampler.mask)
 
@@ -136,11 +193,13 @@ class Splainference:
         self.store.set_label(key, LABEL_READY)
         self.store.bump(key)
 
-    def process(self, key: str) -> int:
+    def _begin(self, key: str):
+        """Read the request, flip WAITING -> SERVICING and write the formatted prompt into the slot:
+        (start epoch, prompt token ids, bytes written, start time), or None when the key is skipped or failed."""
         s = self.store
         user_msg, start = self._read_request(key)
         if user_msg is None:
-            return 0
+            return None
         system_msg = ""
         if self.system_prompt_key:
             v = s.get(self.system_prompt_key)
@@ -159,58 +218,92 @@ class Splainference:
         if not ids:
             debug_post(s, f"[splainference][ERROR]: Tokenization failed for key: {key}")
             self._finish(key)
-            return 0
-        max_val = s.max_val
-        pb = prompt.encode("utf-8")[:max_val]
+            return None
+        pb = prompt.encode("utf-8")[: s.max_val]
         s.set(key, pb)
-        written = len(pb)
         t0 = time.perf_counter_ns()
-        self.model.reset()
-        ctx_room = self.model.cfg.n_ctx - len(ids)
-        if ctx_room <= 0:
+        if self.model.cfg.n_ctx - len(ids) <= 0:
             debug_post(s, f"[splainference][ERROR]: Prefill decode failed for key: {key}")
             self._finish(key)
+            return None
+        return start, ids, len(pb), t0
+
+    def _done(self, key: str, t0: int) -> None:
+        from ..store import TIME_CTIME
+        s = self.store
+        s.set_time(key, TIME_CTIME, int(time.time()), (time.perf_counter_ns() - t0) // 1000)
+        self._finish(key)
+        debug_post(s, f"[splainference][DONE]: Completion written to key: {key}")
+
+    def process(self, key: str) -> int:
+        began = self._begin(key)
+        if began is None:
             return 0
+        start, ids, written, t0 = began
+        self.model.reset()
+        ctx_room = self.model.cfg.n_ctx - len(ids)
         eng = self.engine
         if eng is not None:  # GPU: prefill + device sampler, then one graph replay per token
             t = eng.first_token(ids)
         else:
             logits = self.model.forward(ids)
-        chunk, run, rebid, oom = b"", 0, 0, False
-        for _ in range(min(self.max_tokens, ctx_room)):
-            if not _running:
-                break
+        out = CompletionStream(self.store, self.tok, key, written, min(self.max_tokens, ctx_room))
+        while _running and out.left > 0:
             if eng is None:
                 t = self.sampler(logits)
-            if self.tok.is_eog(t):  # EOS / EOT / end-of-turn (llama_vocab_is_eog, reference :310)
+            if not out.take(t):
                 break
-            piece = self.tok.piece(t)
-            chunk += piece
-            run += 1
             if eng is not None:
                 t = eng.next_token()
             else:
                 logits = self.model.forward([t])
-            if (is_word_boundary(piece) or run >= TOKEN_FLUSH_MAX) and chunk:
-                if written + len(chunk) > max_val:
-                    debug_post(s, f"[splainference][WARN]: Slot full, truncating completion: {key}")
-                    if max_val - written > 0:
-                        s.append(key, chunk[: max_val - written])
-                    oom = True
-                    break
-                written = s.append(key, chunk)
-                chunk, run = b"", 0
-                rebid += TOKEN_FLUSH_MAX
-                if rebid >= SHARD_REBID_TOKENS:
-                    s.shard_rebid(SHARD_ID, INTENT_WILLNEED, SHARD_PRIO_LIVE, SHARD_DUR_LIVE)
-                    rebid = 0
-        if chunk and not oom and max_val - written > 0:
-            s.append(key, chunk[: max_val - written])
-        from ..store import TIME_CTIME
-        s.set_time(key, TIME_CTIME, int(time.time()), (time.perf_counter_ns() - t0) // 1000)
-        self._finish(key)
-        debug_post(s, f"[splainference][DONE]: Completion written to key: {key}")
+            if not out.flush_if_due():
+                break
+        out.close()
+        self._done(key, t0)
         return start
+
+    def serve_batch(self) -> int:
+        """--batch N: decode up to N requests together until no key is WAITING and none is in flight.  Between
+        two shared steps WAITING keys are admitted into free slots (their prefill stalls the others for its
+        duration); after a step every request streams its own token.  A request's seed is the daemon seed XOR
+        the key's hash, so its completion does not depend on what shares its steps.  Returns requests served."""
+        eng = self.batch_engine
+        live = {}  # slot -> [key, stream, t0, next token]
+        served = 0
+
+        def finish(slot):
+            key, out, t0, _ = live.pop(slot)
+            out.close()
+            eng.release(slot)
+            self._done(key, t0)
+
+        while True:
+            if _running:
+                for key in self.waiting():
+                    if len(live) >= eng.S or not _running:
+                        break
+                    began = self._begin(key)
+                    if began is None:
+                        continue
+                    _, ids, written, t0 = began
+                    from ..store import hash_key
+                    slot, t = eng.admit(ids, seed=self.sampler.seed ^ hash_key(key))
+                    budget = min(self.max_tokens, self.model.cfg.n_ctx - len(ids))
+                    live[slot] = [key, CompletionStream(self.store, self.tok, key, written, budget), t0, t]
+                    served += 1
+            if not live:
+                return served
+            for slot in list(live):
+                if not _running or not live[slot][1].take(live[slot][3]):
+                    finish(slot)
+            if not live:
+                continue
+            toks = eng.step()
+            for slot in list(live):
+                live[slot][3] = toks[slot]
+                if not live[slot][1].flush_if_due():
+                    finish(slot)
 
     def waiting(self):
         return [k for k, _ in self.store.enumerate(LABEL_WAITING)]
@@ -225,6 +318,9 @@ def main(argv=None) -> int:
     ap.add_argument("--max-tokens", type=int, default=256)
     ap.add_argument("--seed", type=int, default=0xFFFFFFFF)
     ap.add_argument("--poll-ms", type=int, default=50)
+    ap.add_argument("--batch", type=int, default=1,
+                    help="GPU: decode up to N (2..16) requests together, one shared step per token; 1 (default) "
+                         "serves one request at a time")
     ap.add_argument("--device", default=None, help="cuda (default when a GPU is present) or cpu")
     ap.add_argument("--quant", default="auto", choices=["auto", "bf16", "q4"],
                     help="weights in HBM: q4 = 4-bit Q4G32 (decode streams 0.625 B per weight), bf16, or auto "
@@ -235,6 +331,9 @@ def main(argv=None) -> int:
     a = ap.parse_args(argv)
     if not 0 <= a.group < 64:
         print("Error: signal_group_id must be 0-63.", file=sys.stderr)
+        return 1
+    if not 1 <= a.batch <= 16:
+        print("Error: --batch must be 1-16.", file=sys.stderr)
         return 1
     import torch
     from ..store import Store
@@ -265,12 +364,15 @@ def main(argv=None) -> int:
             model.cfg.n_ctx = min(a.n_ctx, model.cos.shape[0])
     print(f"[Startup]: context window = {model.cfg.n_ctx} tokens, {model.quant} weights.", flush=True)
     sampler = Sampler(seed=a.seed, mask=tok.printable_mask(model.cfg.vocab))
-    d = Splainference(store, model, tok, sampler, a.system_prompt_key, a.max_tokens)
+    d = Splainference(store, model, tok, sampler, a.system_prompt_key, a.max_tokens, a.batch)
     pending = d.waiting()
     if pending:
         print(f"[Startup]: {len(pending)} waiting key(s) found at cold start.", flush=True)
-        for k in pending:
-            d.process(k)
+        if d.batch_engine is not None:
+            d.serve_batch()
+        else:
+            for k in pending:
+                d.process(k)
     if a.oneshot:
         store.shard_release(SHARD_ID)
         store.close()
@@ -283,10 +385,13 @@ def main(argv=None) -> int:
         if cur == last:
             time.sleep(a.poll_ms / 1e3)
             continue
-        for k in d.waiting():
-            if not _running:
-                break
-            d.process(k)
+        if d.batch_engine is not None:
+            d.serve_batch()
+        else:
+            for k in d.waiting():
+                if not _running:
+                    break
+                d.process(k)
         last = cur
     print("\n[Signal]: Shutting down splainference safely...")
     debug_post(store, "[splainference]: Daemon shutting down.")

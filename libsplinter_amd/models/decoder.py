@@ -275,6 +275,25 @@ class CausalLM:
             self.L.dec_q8_quantize.restype = c_int
             self.L.dec_q8_dequant.argtypes = [P, P, c_long, c_int, P, P]
             self.L.dec_q8_dequant.restype = c_int
+            # the batched step (csrc/hip/decoder_batch.hip)
+            for name in ("dec_gemm_small", "dec_gemm_small_q4", "dec_gemm_small_q8"):
+                planes = [P] if name == "dec_gemm_small" else [P, P]
+                getattr(self.L, name).argtypes = [c_int, P, c_long, c_int] + planes + [c_int, c_int, P, c_long, P,
+                                                                                      c_long, P]
+                getattr(self.L, name).restype = c_int
+            self.L.dec_embed_tok_b.argtypes = [P, c_int, P, c_int, P, c_long, P]
+            self.L.dec_embed_tok_b.restype = c_int
+            self.L.dec_rope_kv_b.argtypes = [P, c_long, c_int, c_int, c_int, c_int, P, P, P, P, P, c_long, c_long, P]
+            self.L.dec_rope_kv_b.restype = c_int
+            self.L.dec_attn_b_ws_floats.argtypes = [c_int, c_int, c_int]
+            self.L.dec_attn_b_ws_floats.restype = c_long
+            self.L.dec_attn_decode_b.argtypes = [P, c_long, P, P, c_long, c_long, c_int, c_int, c_int, c_int, c_int,
+                                                 c_float, P, c_long, P, P, P]
+            self.L.dec_attn_decode_b.restype = c_int
+            self.L.dec_sample_b_ws_floats.argtypes = [c_int]
+            self.L.dec_sample_b_ws_floats.restype = c_long
+            self.L.dec_sample_b.argtypes = [P, c_long, c_int, c_int, P, c_float, c_float, P, c_int, P, P, P]
+            self.L.dec_sample_b.restype = c_int
             self.L._dec_declared = True
 
     @classmethod
@@ -545,6 +564,194 @@ class DecodeEngine:
         self.m.pos += 1
         self.steps += 1
         return int(self.host_tok[0])
+
+
+class BatchDecodeEngine:
+    """Up to ``max_seqs`` generations decoded together (csrc/hip/decoder_batch.hip): a decode step
+    streams every projection weight once whatever the number of sequences, so one step serves every
+    live sequence -- per layer dec_rmsnorm, the qkv small GEMM, dec_rope_kv_b, dec_attn_decode_b, the
+    o small GEMM + residual, dec_rmsnorm, the up|gate small GEMM + SwiGLU, the down small GEMM +
+    residual; then the final dec_rmsnorm, the head small GEMM and dec_sample_b -- captured once as a
+    HIP graph on one stream (two graphs, as DecodeEngine: span <= 512 and span = capacity, picked by
+    the longest live sequence).  The launches are always sized for ``max_seqs``; which slots are live
+    is device state ({pos, token, step, active, seed} per slot), so ``admit`` and ``release`` never
+    recapture.  Each slot draws from its own seed and draw index: a sequence's tokens do not depend on
+    what shares its steps.
+
+    ``admit`` prefills the prompt with the eager ``CausalLM.forward`` into the slot's cache between
+    two steps; the other sequences wait for its duration.  Chunked prefill, prefill overlapped with
+    decode and batched prefill of several prompts are out of scope."""
+
+    ST_WORDS = 8
+
+    def __init__(self, model: "CausalLM", max_seqs: int = 8, top_p: float = 0.9, temp: float = 0.7,
+                 seed: int = 0xFFFFFFFF, mask: Optional[torch.Tensor] = None, use_graph: bool = True):
+        assert model.hip, "BatchDecodeEngine runs on the GPU"
+        if not 2 <= max_seqs <= 16:
+            raise ValueError(f"max_seqs must be 2..16, not {max_seqs}")
+        if not model.decode_kernel:
+            raise ValueError(f"head dim {model.cfg.head_dim}: the batched decode engine needs a multiple of 64 "
+                             "up to 256 (use CausalLM.forward)")
+        m, cfg = model, model.cfg
+        self.m, self.S = m, int(max_seqs)
+        self.top_p, self.temp, self.seed = float(top_p), float(temp), int(seed) & 0xFFFFFFFFFFFFFFFF
+        dev, S = m.device, self.S
+        kvd = cfg.kv_heads * cfg.head_dim
+        need = S * cfg.layers * 2 * cfg.n_ctx * kvd * 2
+        free = torch.cuda.mem_get_info(torch.device(dev))[0]
+        if need > free:
+            raise RuntimeError(f"KV cache for {S} sequences x {cfg.n_ctx} tokens needs {need >> 20} MiB, "
+                               f"{free >> 20} MiB of device memory are free: lower max_seqs or the context")
+        self.kv = torch.zeros((S, cfg.layers, 2, cfg.n_ctx, cfg.kv_heads, cfg.head_dim), dtype=torch.bfloat16,
+                              device=dev)
+        z = lambda n, dt=torch.bfloat16: torch.zeros((S, n), dtype=dt, device=dev)  # noqa: E731
+        self.xa, self.xb, self.h = z(cfg.d), z(cfg.d), z(cfg.d)
+        self.qkv, self.attn, self.ffn = z(cfg.d + 2 * kvd), z(cfg.d), z(cfg.ffn)
+        self.logits = z(m.head.shape[0], torch.float32)
+        self.st = torch.zeros((S, self.ST_WORDS), dtype=torch.int32, device=dev)
+        self.attn_ws = torch.empty(m.L.dec_attn_b_ws_floats(S, cfg.heads, cfg.head_dim), dtype=torch.float32,
+                                   device=dev)
+        self.samp_ws = torch.empty(m.L.dec_sample_b_ws_floats(S), dtype=torch.float32, device=dev)
+        self.host_tok = torch.full((S,), -1, dtype=torch.int32).pin_memory()
+        self._rec = torch.zeros(self.ST_WORDS, dtype=torch.int32).pin_memory()
+        self.mask = mask[: cfg.vocab].to(device=dev, dtype=torch.uint8).contiguous() if mask is not None else None
+        self.use_graph = use_graph
+        self.graphs = {}                      # attention span (512 or the capacity) -> captured step
+        self.pos: List[Optional[int]] = [None] * S   # host mirror of each live slot's position
+        self.steps = 0
+
+    # ---------------------------------------------------------------- slots --
+    def active(self) -> List[int]:
+        return [b for b, p in enumerate(self.pos) if p is not None]
+
+    def _write_state(self, slot: int, words: List[int]):
+        for i, w in enumerate(words):
+            w &= 0xFFFFFFFF
+            self._rec[i] = w - (1 << 32) if w >= 1 << 31 else w
+        self.st[slot].copy_(self._rec, non_blocking=True)
+        torch.cuda.current_stream().synchronize()  # _rec is reused by the next write
+
+    def admit(self, ids: List[int], seed: Optional[int] = None):
+        """Prefill ``ids`` into a free slot and sample its first token: (slot, first_token)."""
+        m = self.m
+        free = [b for b, p in enumerate(self.pos) if p is None]
+        if not free:
+            raise RuntimeError(f"all {self.S} sequence slots are in use")
+        if not ids or len(ids) >= m.cfg.n_ctx:
+            raise ValueError(f"a prompt of {len(ids)} tokens leaves no room in a context of {m.cfg.n_ctx}")
+        slot = free[0]
+        saved = (m.kv, m.pos)
+        m.kv, m.pos = self.kv[slot], 0  # the eager forward appends to whatever cache the model points at
+        try:
+            logits = m.forward(ids)
+        finally:
+            m.kv, m.pos = saved
+        sd = self.seed if seed is None else int(seed) & 0xFFFFFFFFFFFFFFFF
+        self._write_state(slot, [len(ids), 0, 0, 1, sd & 0xFFFFFFFF, sd >> 32, 0, 0])
+        self.logits[slot, : m.cfg.vocab].copy_(logits)
+        self._sample(slot, 1, inc_pos=0)
+        torch.cuda.current_stream().synchronize()
+        self.pos[slot] = len(ids)
+        return slot, int(self.host_tok[slot])
+
+    def release(self, slot: int):
+        """Retire a sequence: the slot is skipped by every later step until it is admitted again."""
+        if self.pos[slot] is None:
+            raise ValueError(f"slot {slot} is not in use")
+        self._write_state(slot, [0] * self.ST_WORDS)
+        self.pos[slot] = None
+
+    def set_token(self, slot: int, tok: int):
+        """Replace the token the slot's next step consumes (teacher forcing)."""
+        self.st[slot, 1] = int(tok)
+
+    # ----------------------------------------------------------------- step --
+    def _sample(self, slot0: int, n: int, inc_pos: int):
+        from .nomic import _chk, _stream
+        m, lg = self.m, self.logits
+        _chk(m.L.dec_sample_b(lg[slot0].data_ptr(), lg.stride(0), n, m.cfg.vocab,
+                              self.mask.data_ptr() if self.mask is not None else None, self.top_p, self.temp,
+                              self.st[slot0].data_ptr(), inc_pos, self.host_tok[slot0:].data_ptr(),
+                              self.samp_ws[slot0 * (self.samp_ws.numel() // self.S):].data_ptr(), _stream()), "sample_b")
+
+    def _mm(self, mode, x, w, N, K, res, out, what):
+        from .nomic import _chk, _stream
+        L, S = self.m.L, self.S
+        rp, ldr = (res.data_ptr(), res.stride(0)) if res is not None else (None, 0)
+        if isinstance(w, Q4Weight):
+            fn = L.dec_gemm_small_q8 if w.bits == 8 else L.dec_gemm_small_q4
+            rc = fn(mode, x.data_ptr(), x.stride(0), S, w.q.data_ptr(), w.sm.data_ptr(), N, K, rp, ldr,
+                    out.data_ptr(), out.stride(0), _stream())
+        else:
+            rc = L.dec_gemm_small(mode, x.data_ptr(), x.stride(0), S, w.data_ptr(), N, K, rp, ldr, out.data_ptr(),
+                                  out.stride(0), _stream())
+        _chk(rc, what)
+
+    def _enqueue_step(self, span: int):
+        from .nomic import _chk, _stream
+        m, cfg, L, S = self.m, self.m.cfg, self.m.L, self.S
+        s = _stream()
+        H, KVH, hd = cfg.heads, cfg.kv_heads, cfg.head_dim
+        st = self.st.data_ptr()
+
+        def rms(x, w, out):
+            _chk(L.dec_rmsnorm(x.data_ptr(), x.stride(0), w.data_ptr(), S, cfg.d, cfg.eps, out.data_ptr(),
+                               out.stride(0), s), "rmsnorm")
+
+        _chk(L.dec_embed_tok_b(m.emb.data_ptr(), cfg.d, st, S, self.xa.data_ptr(), self.xa.stride(0), s), "embed_tok_b")
+        for li, lw in enumerate(m.layers):
+            rms(self.xa, lw["n1"], self.h)
+            self._mm(0, self.h, lw["qkv"], lw["qkv"].shape[0], cfg.d, None, self.qkv, "gemm qkv")
+            kc, vc = self.kv[0, li, 0], self.kv[0, li, 1]
+            _chk(L.dec_rope_kv_b(self.qkv.data_ptr(), self.qkv.stride(0), S, H, KVH, hd, m.cos.data_ptr(),
+                                 m.sin.data_ptr(), st, kc.data_ptr(), vc.data_ptr(), KVH * hd, self.kv.stride(0), s),
+                 "rope_kv_b")
+            _chk(L.dec_attn_decode_b(self.qkv.data_ptr(), self.qkv.stride(0), kc.data_ptr(), vc.data_ptr(), KVH * hd,
+                                     self.kv.stride(0), span, S, H, KVH, hd, hd ** -0.5, self.attn.data_ptr(),
+                                     self.attn.stride(0), st, self.attn_ws.data_ptr(), s), "attn_decode_b")
+            self._mm(1, self.attn, lw["o"], cfg.d, cfg.d, self.xa, self.xb, "gemm o")
+            rms(self.xb, lw["n2"], self.h)
+            self._mm(2, self.h, lw["ug"], lw["ug"].shape[0], cfg.d, None, self.ffn, "gemm up|gate")
+            self._mm(1, self.ffn, lw["down"], cfg.d, cfg.ffn, self.xb, self.xa, "gemm down")
+        rms(self.xa, m.norm_out, self.h)
+        self._mm(4, self.h, m.head, m.head.shape[0], cfg.d, None, self.logits, "gemm head")
+        self._sample(0, S, inc_pos=1)
+
+    def step(self) -> Dict[int, int]:
+        """One decode step for every live slot: {slot: sampled token}."""
+        live = self.active()
+        if not live:
+            return {}
+        n_ctx = self.m.cfg.n_ctx
+        for b in live:
+            if self.pos[b] >= n_ctx:
+                raise ValueError(f"slot {b}: context window of {n_ctx} tokens exceeded")
+        span = n_ctx if max(self.pos[b] for b in live) + 1 > 512 else min(512, n_ctx)
+        if not self.use_graph:
+            self._enqueue_step(span)
+        else:
+            g = self.graphs.get(span)
+            if g is None:
+                # warm up once outside capture (first-launch code-object loading), then capture
+                side = torch.cuda.Stream()
+                side.wait_stream(torch.cuda.current_stream())
+                saved = self.st.clone()
+                with torch.cuda.stream(side):
+                    self._enqueue_step(span)
+                torch.cuda.current_stream().wait_stream(side)
+                self.st.copy_(saved)  # the warm-up step is undone: same state, cache rows rewritten next
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    self._enqueue_step(span)
+                self.graphs[span] = g
+            g.replay()
+        torch.cuda.current_stream().synchronize()
+        self.steps += 1
+        out = {}
+        for b in live:
+            self.pos[b] += 1
+            out[b] = int(self.host_tok[b])
+        return out
 
 
 class Sampler:
