@@ -260,6 +260,49 @@ __global__ void k_rope_kv_b(uint16_t* __restrict__ qkv, long ldq, int H, int KVH
   }
 }
 
+// RoPE + cache append of a batched prefill pass (BatchDecodeEngine.prefill): blockIdx.y is a segment of the
+// by-value table, one thread per 8 columns of a packed qkv row.  q columns rotate in place at the row's own
+// position pos0 + r with k_rope's statements (so its bits); a k chunk is rotated the same way and stored at
+// row pos0 + r of the slot's cache instead of back into qkv, a v chunk is copied there: the cache holds what
+// dec_rope followed by the two slice copies of CausalLM.forward leaves.  The k columns of qkv stay
+// unrotated; nothing reads them afterwards.
+__global__ __launch_bounds__(256) void k_rope_kv_seg(uint16_t* __restrict__ qkv, long ld, int H, int KVH, int hd,
+                                                     const float* __restrict__ cs, const float* __restrict__ sn,
+                                                     uint16_t* __restrict__ kc, uint16_t* __restrict__ vc, long ldkv,
+                                                     PrefillSegs tb) {
+  const PrefillSeg sg = prefill_seg_at(tb, blockIdx.y);
+  const int qcols = H * hd, qk = qcols + KVH * hd;
+  const int per_row = (qk + KVH * hd) >> 3;
+  const long total = (long)sg.n * per_row;
+  const int half = hd >> 1;
+  qkv += (long)sg.row0 * ld;
+  kc += (long)sg.slot * tb.seq_stride;
+  vc += (long)sg.slot * tb.seq_stride;
+  for (long q = blockIdx.x * (long)blockDim.x + threadIdx.x; q < total; q += (long)gridDim.x * blockDim.x) {
+    const long row = q / per_row;
+    const int col = (int)(q - row * per_row) * 8;
+    const long p = sg.pos0 + row;
+    uint16_t* ptr = qkv + row * ld + col;
+    if (col >= qk) {
+      *(uint4*)(vc + p * ldkv + (col - qk)) = *(const uint4*)ptr;
+      continue;
+    }
+    const int i0 = (col % hd) >> 1;  // first pair index inside the head
+    float f[8], o[8];
+    unpack8(*(const uint4*)ptr, f);
+    const float4 c4 = *(const float4*)(cs + p * half + i0), s4 = *(const float4*)(sn + p * half + i0);
+    const float c[4] = {c4.x, c4.y, c4.z, c4.w}, s[4] = {s4.x, s4.y, s4.z, s4.w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float a = f[2 * e], b = f[2 * e + 1];
+      o[2 * e] = a * c[e] - b * s[e];
+      o[2 * e + 1] = a * s[e] + b * c[e];
+    }
+    uint16_t* dst = col < qcols ? ptr : kc + p * ldkv + (col - qcols);
+    *(uint4*)dst = pack8(o);
+  }
+}
+
 // ------------------------------------------------------------------ decode attention --
 // The four kernels of dec_attn_decode_ws with the slot in blockIdx.z: the slot's query row, cache, output row
 // and workspace slice, and its length st[b].pos + 1.  A slot shorter than the captured span runs empty
@@ -1088,6 +1131,31 @@ int dec_rope_kv_b(void* qkv, long ldq, int nseq, int H, int KVH, int hd, const f
   hipLaunchKernelGGL(k_rope_kv_b, dim3((unsigned)((work + 255) / 256), (unsigned)nseq), dim3(256), 0, s,
                      (uint16_t*)qkv, ldq, H, KVH, hd, cos_tab, sin_tab, st, (uint16_t*)kc, (uint16_t*)vc, ldkv,
                      seq_stride);
+  return (int)hipGetLastError();
+}
+
+// RoPE + cache append for up to 16 prompt chunks in one launch (k_rope_kv_seg).  qkv: packed bf16 rows
+// [T, ldq] of (H + 2 KVH) hd; segs: HOST int32 [nseg][4] = {row0, n, pos0, slot}, checked and passed by
+// value as dec_attn_prefill_kv_seg does (hipErrorInvalidValue and nothing launched when a check fails);
+// kc / vc: slot 0's layer cache [n_ctx, ldkv], slot b's at + b * seq_stride elements; cos / sin fp32
+// [n_ctx, hd / 2].  Row row0 + r of a segment rotates its q columns in place at position pos0 + r and puts
+// its rotated k and its v at cache row pos0 + r of the segment's slot: the bits of dec_rope + slice copies.
+int dec_rope_kv_seg(void* qkv, long ldq, long T, const int32_t* segs, int nseg, int H, int KVH, int hd,
+                    const float* cos_tab, const float* sin_tab, void* kc, void* vc, long ldkv, long seq_stride,
+                    int nslots, int n_ctx, hipStream_t s) {
+  PrefillSegs tb;
+  if (H <= 0 || KVH <= 0 || H % KVH || (hd != 64 && hd != 128) || ldq % 8 || ldkv % 8 || seq_stride % 8 ||
+      ldq < (long)(H + 2 * KVH) * hd || ldkv < (long)KVH * hd || seq_stride < (long)n_ctx * ldkv || !qkv || !kc ||
+      !vc || !cos_tab || !sin_tab ||
+      ((uintptr_t)qkv | (uintptr_t)kc | (uintptr_t)vc | (uintptr_t)cos_tab | (uintptr_t)sin_tab) & 15 ||
+      !prefill_segs_build(segs, nseg, T, nslots, n_ctx, seq_stride, tb))
+    return (int)hipErrorInvalidValue;
+  int nmax = 0;
+  for (int i = 0; i < tb.nseg; ++i) nmax = tb.n[i] > nmax ? tb.n[i] : nmax;
+  long g = ((long)nmax * ((H + 2 * KVH) * hd / 8) + 255) / 256;
+  if (g > 1024) g = 1024;
+  hipLaunchKernelGGL(k_rope_kv_seg, dim3((unsigned)g, (unsigned)tb.nseg), dim3(256), 0, s, (uint16_t*)qkv, ldq, H, KVH,
+                     hd, cos_tab, sin_tab, (uint16_t*)kc, (uint16_t*)vc, ldkv, tb);
   return (int)hipGetLastError();
 }
 

@@ -32,6 +32,52 @@ __device__ __forceinline__ uint4 pack8(const float* f) {
 // [3] active (0 / 1), [4] [5] the slot's sampler seed (low, high half), [6] [7] reserved (zero).
 enum { ST_POS = 0, ST_TOK = 1, ST_STEP = 2, ST_ACTIVE = 3, ST_SEED_LO = 4, ST_SEED_HI = 5, ST_WORDS = 8 };
 
+// Batched prompt prefill (dec_rope_kv_seg, dec_attn_prefill_kv_seg): up to 16 segments of the packed token
+// matrix.  Segment i owns rows row0 .. row0 + n - 1, the tokens at absolute positions pos0 .. pos0 + n - 1
+// of the prompt in cache slot `slot` (the slot's cache at + slot * seq_stride elements).  The launchers
+// validate the host array and pass this table BY VALUE in the kernel arguments: no device table, no copy,
+// and a kernel touches no row the validated table does not name.
+constexpr int kMaxSegs = 16;
+struct PrefillSegs {
+  int nseg;
+  int row0[kMaxSegs], n[kMaxSegs], pos0[kMaxSegs], slot[kMaxSegs];
+  long seq_stride;
+};
+struct PrefillSeg {
+  int row0, n, pos0, slot;
+};
+
+// segs: int32 [nseg][4] = {row0, n, pos0, slot}.  False: a segment is empty, leaves the T rows, the nslots
+// slots or the n_ctx cache rows, two segments share token rows or a slot, or there are not 1..16 of them
+inline bool prefill_segs_build(const int32_t* segs, int nseg, long T, int nslots, int n_ctx, long seq_stride,
+                               PrefillSegs& tb) {
+  if (!segs || nseg < 1 || nseg > kMaxSegs || T <= 0 || nslots <= 0 || n_ctx <= 0) return false;
+  tb = PrefillSegs{};
+  tb.nseg = nseg;
+  tb.seq_stride = seq_stride;
+  for (int i = 0; i < nseg; ++i) {
+    const long row0 = segs[4 * i], n = segs[4 * i + 1], pos0 = segs[4 * i + 2], slot = segs[4 * i + 3];
+    if (n < 1 || row0 < 0 || row0 + n > T || slot < 0 || slot >= nslots || pos0 < 0 || pos0 + n > n_ctx) return false;
+    for (int j = 0; j < i; ++j)
+      if (slot == tb.slot[j] || (row0 < (long)tb.row0[j] + tb.n[j] && tb.row0[j] < row0 + n)) return false;
+    tb.row0[i] = (int)row0;
+    tb.n[i] = (int)n;
+    tb.pos0[i] = (int)pos0;
+    tb.slot[i] = (int)slot;
+  }
+  return true;
+}
+
+// segment i of the table with i uniform over the workgroup: selects over the unrolled table, so the by-value
+// argument is read with constant offsets and never copied to scratch
+__device__ __forceinline__ PrefillSeg prefill_seg_at(const PrefillSegs& tb, int i) {
+  PrefillSeg s{0, 0, 0, 0};
+#pragma unroll
+  for (int j = 0; j < kMaxSegs; ++j)
+    if (j == i) s = PrefillSeg{tb.row0[j], tb.n[j], tb.pos0[j], tb.slot[j]};
+  return s;
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

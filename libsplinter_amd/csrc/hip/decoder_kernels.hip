@@ -1324,18 +1324,52 @@ __device__ __forceinline__ float pa_xg_sum(float x) {
   return __uint_as_float(q[0]) + __uint_as_float(q[1]);
 }
 
-template <int HD>
+// SEG: empty for one prompt chunk (dec_attn_prefill_kv), or one PrefillSegs table by value
+// (dec_attn_prefill_kv_seg): the grid is then the sum over the segments of q-blocks x heads, ordered
+// segment, head, q-block, so the q-blocks of one (segment, head) are neighbours under the XCD remap; a
+// block finds its segment, takes n / pos0 from it and moves the q / out / cache bases to the segment's rows
+// and slot.  q-blocks start at the segment's first row, so everything below is the single-chunk kernel on
+// that segment alone.  The parameter pack keeps the signature, and with it the code, of the two
+// single-chunk instantiations as they were (profiles/prefill_batch/README.md).
+template <int HD, class... SEG>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k_prefill_attn(const uint16_t* __restrict__ qg, long ldq,
                                                       const uint16_t* __restrict__ kc,
                                                       const uint16_t* __restrict__ vc, long ldkv, int n, int pos0,
                                                       int heads, int kv_heads, float scale_log2,
-                                                      uint16_t* __restrict__ out, long ldo) {
+                                                      uint16_t* __restrict__ out, long ldo, SEG... seg) {
+  static_assert(sizeof...(SEG) <= 1, "at most one segment table");
   constexpr int KT = HD == 128 ? 32 : 64, RB = HD * 2, NCH = HD / 8, NKK = HD / 32, NDB = HD / 16, NL = KT * NCH / 256;
   __shared__ __attribute__((aligned(16))) char lds[2][2][KT * RB];  // [buf][K | V][key * RB]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, li = lane & 15;
   const int nwg = gridDim.x, orig = blockIdx.x, q8 = nwg / 8, r8 = nwg % 8, xcd = orig % 8;
   const int lid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + orig / 8;
-  const int nqb = nwg / heads, head = lid / nqb, qstart = (lid - head * nqb) * 128;
+  int head, qstart;
+  if constexpr (sizeof...(SEG) == 0) {
+    const int nqb = nwg / heads;
+    head = lid / nqb;
+    qstart = (lid - head * nqb) * 128;
+  } else {
+    const PrefillSegs& tb = (seg, ...);
+    int rem = lid, si = 0;
+#pragma unroll
+    for (int j = 0; j < kMaxSegs - 1; ++j) {  // the launcher sized the grid: lid falls inside the table
+      const int w = ((tb.n[j] + 127) >> 7) * heads;
+      if (j == si && j + 1 < tb.nseg && rem >= w) {
+        rem -= w;
+        si = j + 1;
+      }
+    }
+    const PrefillSeg sg = prefill_seg_at(tb, si);
+    const int nqb = (sg.n + 127) >> 7;
+    head = rem / nqb;
+    qstart = (rem - head * nqb) * 128;
+    n = sg.n;
+    pos0 = sg.pos0;
+    qg += (long)sg.row0 * ldq;
+    out += (long)sg.row0 * ldo;
+    kc += (long)sg.slot * tb.seq_stride;
+    vc += (long)sg.slot * tb.seq_stride;
+  }
   const int kvhead = head / (heads / kv_heads);
   const long lenk = (long)pos0 + n;
   auto ksw = [](int key, int c) { return c ^ (key & (NCH - 1)); };
@@ -1603,6 +1637,35 @@ int dec_attn_prefill_kv(const void* q, long ldq, const void* k, const void* v, l
   else
     hipLaunchKernelGGL(k_prefill_attn<128>, dim3(nqb * H), dim3(256), 0, s, (const uint16_t*)q, ldq,
                        (const uint16_t*)k, (const uint16_t*)v, ldkv, n, pos0, H, KVH, sl2, (uint16_t*)out, ldo);
+  return (int)hipGetLastError();
+}
+
+// dec_attn_prefill_kv over up to 16 prompt chunks in one launch.  q rows [T, ldq] and out rows [T, ldo]
+// are packed; segs: HOST int32 [nseg][4] = {row0, n, pos0, slot} (decoder_common.hpp PrefillSegs): rows
+// row0 .. row0+n-1 are the tokens at positions pos0 .. pos0+n-1 of the prompt in cache slot `slot`; k / v:
+// slot 0's layer cache rows [n_ctx, ldkv], slot b's at + b * seq_stride elements.  The table is checked
+// here (n >= 1, rows inside T and disjoint, slot < nslots and used once, 0 <= pos0, pos0 + n <= n_ctx;
+// alignment and head dim as dec_attn_prefill_kv) and passed by value; hipErrorInvalidValue with nothing
+// launched when a check fails.  A segment's output is bit-identical to dec_attn_prefill_kv on it alone.
+int dec_attn_prefill_kv_seg(const void* q, long ldq, long T, const int32_t* segs, int nseg, const void* k,
+                            const void* v, long ldkv, long seq_stride, int nslots, int n_ctx, int H, int KVH, int hd,
+                            float scale, void* out, long ldo, hipStream_t s) {
+  PrefillSegs tb;
+  if (H <= 0 || KVH <= 0 || H % KVH || (hd != 64 && hd != 128) || ldq % 8 || ldkv % 8 || ldo % 8 || seq_stride % 8 ||
+      ldq < (long)H * hd || ldkv < (long)KVH * hd || ldo < (long)H * hd || seq_stride < (long)n_ctx * ldkv ||
+      !q || !k || !v || !out || ((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out) & 15 ||
+      !prefill_segs_build(segs, nseg, T, nslots, n_ctx, seq_stride, tb))
+    return (int)hipErrorInvalidValue;
+  long blocks = 0;
+  for (int i = 0; i < tb.nseg; ++i) blocks += (long)((tb.n[i] + 127) / 128) * H;
+  if (blocks > 0x7fffffffL) return (int)hipErrorInvalidValue;
+  const float sl2 = scale * 1.4426950408889634f;
+  if (hd == 64)
+    hipLaunchKernelGGL((k_prefill_attn<64, PrefillSegs>), dim3((unsigned)blocks), dim3(256), 0, s, (const uint16_t*)q,
+                       ldq, (const uint16_t*)k, (const uint16_t*)v, ldkv, 0, 0, H, KVH, sl2, (uint16_t*)out, ldo, tb);
+  else
+    hipLaunchKernelGGL((k_prefill_attn<128, PrefillSegs>), dim3((unsigned)blocks), dim3(256), 0, s, (const uint16_t*)q,
+                       ldq, (const uint16_t*)k, (const uint16_t*)v, ldkv, 0, 0, H, KVH, sl2, (uint16_t*)out, ldo, tb);
   return (int)hipGetLastError();
 }
 

@@ -21,7 +21,9 @@ Contract kept from the reference daemon (/root/reference/splainference.cpp):
           poll the signal group every 50 ms (:570-592)
 Extra flags: --random-init (no GGUF: random llama weights, byte vocabulary,
 printable-byte sampling), --max-tokens (cap per request), --seed, --batch N
-(GPU: up to N requests decoded together, one shared step per token; default 1).
+(GPU: up to N requests decoded together, one shared step per token; default 1), --prefill-chunk C (with
+--batch: WAITING requests are admitted together, C prompt tokens of each per pass; default 0, one whole
+prompt at a time).
 """
 from __future__ import annotations
 
@@ -147,7 +149,7 @@ class CompletionStream:
 
 class Splainference:
     def __init__(self, store, model, tokenizer, sampler, system_prompt_key=None, max_tokens: int = 256,
-                 batch: int = 1):
+                 batch: int = 1, prefill_chunk: int = 0):
         self.store, self.model, self.tok, self.sampler = store, model, tokenizer, sampler
         self.system_prompt_key = system_prompt_key
         self.max_tokens = max_tokens
@@ -164,6 +166,9 @@ class Splainference:
         elif gpu:
             from ..models.decoder import DecodeEngine
             self.engine = DecodeEngine(model, sampler.top_p, sampler.temp, sampler.seed, sampler.mask)
+        # --prefill-chunk C: batched, chunked admission (BatchDecodeEngine.submit / prefill) where the batch
+        # engine serves and the prefill kernels take the head dim; ignored wherever serving is sequential
+        self.prefill_chunk = prefill_chunk if self.batch_engine is not None and model.prefill_kernel else 0
 
     def _read_request(self, key: str):
         s = self.store
@@ -266,11 +271,15 @@ class Splainference:
     def serve_batch(self) -> int:
         """--batch N: decode up to N requests together until no key is WAITING and none is in flight.  Between
         two shared steps WAITING keys are admitted into free slots (their prefill stalls the others for its
-        duration); after a step every request streams its own token.  A request's seed is the daemon seed XOR
+        duration; with --prefill-chunk C they are submitted instead and one pass over the next C prompt tokens
+        of every submitted request runs before each step, a request's stream starting when its first token
+        arrives); after a step every request streams its own token.  A request's seed is the daemon seed XOR
         the key's hash, so its completion does not depend on what shares its steps.  Returns requests served."""
         eng = self.batch_engine
         live = {}  # slot -> [key, stream, t0, next token]
+        pend = {}  # slot -> (key, prompt tokens, bytes written, t0): submitted, first token not drawn yet
         served = 0
+        chunk = self.prefill_chunk
 
         def finish(slot):
             key, out, t0, _ = live.pop(slot)
@@ -281,18 +290,38 @@ class Splainference:
         while True:
             if _running:
                 for key in self.waiting():
-                    if len(live) >= eng.S or not _running:
+                    if len(live) + len(pend) >= eng.S or not _running:
                         break
                     began = self._begin(key)
                     if began is None:
                         continue
                     _, ids, written, t0 = began
                     from ..store import hash_key
-                    slot, t = eng.admit(ids, seed=self.sampler.seed ^ hash_key(key))
+                    seed = self.sampler.seed ^ hash_key(key)
+                    served += 1
+                    if chunk > 0:  # --prefill-chunk: reserve the slot now, prefill with the others below
+                        pend[eng.submit(ids, seed=seed)] = (key, len(ids), written, t0)
+                        continue
+                    slot, t = eng.admit(ids, seed=seed)
                     budget = min(self.max_tokens, self.model.cfg.n_ctx - len(ids))
                     live[slot] = [key, CompletionStream(self.store, self.tok, key, written, budget), t0, t]
-                    served += 1
+            elif pend:
+                # shutdown: a pending request has produced nothing yet.  It is cancelled and closed the way a
+                # live one is: SERVICING -> READY with the formatted prompt and an empty completion, so no key
+                # is left SERVICING with no daemon behind it
+                for slot in list(pend):
+                    key, _, _, t0 = pend.pop(slot)
+                    eng.release(slot)
+                    self._done(key, t0)
+            if pend:
+                # one pass over the next chunk of every pending prompt, then one step for the live slots
+                for slot, t in eng.prefill(chunk).items():
+                    key, n, written, t0 = pend.pop(slot)
+                    budget = min(self.max_tokens, self.model.cfg.n_ctx - n)
+                    live[slot] = [key, CompletionStream(self.store, self.tok, key, written, budget), t0, t]
             if not live:
+                if pend:
+                    continue
                 return served
             for slot in list(live):
                 if not _running or not live[slot][1].take(live[slot][3]):
@@ -321,6 +350,9 @@ def main(argv=None) -> int:
     ap.add_argument("--batch", type=int, default=1,
                     help="GPU: decode up to N (2..16) requests together, one shared step per token; 1 (default) "
                          "serves one request at a time")
+    ap.add_argument("--prefill-chunk", type=int, default=0,
+                    help="with --batch on the GPU: admit WAITING requests together, C prompt tokens of each per "
+                         "pass, one pass between two decode steps; 0 (default) prefills one whole prompt at a time")
     ap.add_argument("--device", default=None, help="cuda (default when a GPU is present) or cpu")
     ap.add_argument("--quant", default="auto", choices=["auto", "bf16", "q4"],
                     help="weights in HBM: q4 = 4-bit Q4G32 (decode streams 0.625 B per weight), bf16, or auto "
@@ -334,6 +366,9 @@ def main(argv=None) -> int:
         return 1
     if not 1 <= a.batch <= 16:
         print("Error: --batch must be 1-16.", file=sys.stderr)
+        return 1
+    if a.prefill_chunk < 0:
+        print("Error: --prefill-chunk must be >= 0.", file=sys.stderr)
         return 1
     import torch
     from ..store import Store
@@ -364,7 +399,7 @@ def main(argv=None) -> int:
             model.cfg.n_ctx = min(a.n_ctx, model.cos.shape[0])
     print(f"[Startup]: context window = {model.cfg.n_ctx} tokens, {model.quant} weights.", flush=True)
     sampler = Sampler(seed=a.seed, mask=tok.printable_mask(model.cfg.vocab))
-    d = Splainference(store, model, tok, sampler, a.system_prompt_key, a.max_tokens, a.batch)
+    d = Splainference(store, model, tok, sampler, a.system_prompt_key, a.max_tokens, a.batch, a.prefill_chunk)
     pending = d.waiting()
     if pending:
         print(f"[Startup]: {len(pending)} waiting key(s) found at cold start.", flush=True)

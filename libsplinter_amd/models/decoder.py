@@ -294,6 +294,13 @@ class CausalLM:
             self.L.dec_sample_b_ws_floats.restype = c_long
             self.L.dec_sample_b.argtypes = [P, c_long, c_int, c_int, P, c_float, c_float, P, c_int, P, P, P]
             self.L.dec_sample_b.restype = c_int
+            # the batched prompt prefill: the segment table is a host int32 [nseg][4] array
+            self.L.dec_rope_kv_seg.argtypes = [P, c_long, c_long, P, c_int, c_int, c_int, c_int, P, P, P, P, c_long,
+                                               c_long, c_int, c_int, P]
+            self.L.dec_rope_kv_seg.restype = c_int
+            self.L.dec_attn_prefill_kv_seg.argtypes = [P, c_long, c_long, P, c_int, P, P, c_long, c_long, c_int, c_int,
+                                                       c_int, c_int, c_int, c_float, P, c_long, P]
+            self.L.dec_attn_prefill_kv_seg.restype = c_int
             self.L._dec_declared = True
 
     @classmethod
@@ -579,8 +586,21 @@ class BatchDecodeEngine:
     what shares its steps.
 
     ``admit`` prefills the prompt with the eager ``CausalLM.forward`` into the slot's cache between
-    two steps; the other sequences wait for its duration.  Chunked prefill, prefill overlapped with
-    decode and batched prefill of several prompts are out of scope."""
+    two steps; the other sequences wait for its duration.
+
+    ``submit`` + ``prefill(chunk)`` is the batched, chunked admission: ``submit`` only reserves a slot
+    on the host (its device record stays inactive, so ``step`` skips it), and one ``prefill`` pass takes
+    the next ``min(chunk, remaining)`` prompt tokens of EVERY pending slot through the layers as one
+    packed token matrix -- per layer dec_rmsnorm, the qkv GEMM, dec_rope_kv_seg, dec_attn_prefill_kv_seg,
+    the o GEMM + residual, dec_rmsnorm, the up|gate GEMM and the down GEMM + residual -- so a weight is
+    streamed (and a 4- / 8-bit one dequantised) once per pass, not once per prompt, and a long prompt
+    holds the live streams for one chunk at a time.  A prompt that ends in the pass gets the final norm
+    and the LM head on its last row, its record, and its first token from dec_sample_b, as ``admit``
+    does.  With a fixed ``chunk`` a request's chunk boundaries sit at multiples of ``chunk`` from its own
+    start, the two segment kernels never look past a segment, and every GEMM of a pass runs on the
+    128 x 128 kernel, whose row results do not depend on the row count or on where a row sits: a
+    request's first token, cache rows and later tokens do not depend on what shares its passes.
+    Prefill overlapped with the decode step on a second stream is out of scope."""
 
     ST_WORDS = 8
 
@@ -619,6 +639,9 @@ class BatchDecodeEngine:
         self.graphs = {}                      # attention span (512 or the capacity) -> captured step
         self.pos: List[Optional[int]] = [None] * S   # host mirror of each live slot's position
         self.steps = 0
+        self.pend: Dict[int, list] = {}       # pending slot -> [prompt ids, tokens prefilled, seed]
+        self._pf: Optional[dict] = None       # prefill workspaces, sized for S * chunk rows
+        self.prefill_passes = 0
 
     # ---------------------------------------------------------------- slots --
     def active(self) -> List[int]:
@@ -634,7 +657,7 @@ class BatchDecodeEngine:
     def admit(self, ids: List[int], seed: Optional[int] = None):
         """Prefill ``ids`` into a free slot and sample its first token: (slot, first_token)."""
         m = self.m
-        free = [b for b, p in enumerate(self.pos) if p is None]
+        free = [b for b, p in enumerate(self.pos) if p is None and b not in self.pend]
         if not free:
             raise RuntimeError(f"all {self.S} sequence slots are in use")
         if not ids or len(ids) >= m.cfg.n_ctx:
@@ -656,6 +679,9 @@ class BatchDecodeEngine:
 
     def release(self, slot: int):
         """Retire a sequence: the slot is skipped by every later step until it is admitted again."""
+        if slot in self.pend:  # a pending prompt is cancelled: its record was never active
+            del self.pend[slot]
+            return
         if self.pos[slot] is None:
             raise ValueError(f"slot {slot} is not in use")
         self._write_state(slot, [0] * self.ST_WORDS)
@@ -664,6 +690,146 @@ class BatchDecodeEngine:
     def set_token(self, slot: int, tok: int):
         """Replace the token the slot's next step consumes (teacher forcing)."""
         self.st[slot, 1] = int(tok)
+
+    # -------------------------------------------------------------- prefill --
+    PF_ROWS = 128  # row multiple of the MFMA GEMM's A operand (nomic_api.h)
+
+    def pending(self) -> List[int]:
+        """Slots reserved by ``submit`` whose prompt is not fully prefilled yet."""
+        return sorted(self.pend)
+
+    def submit(self, ids: List[int], seed: Optional[int] = None) -> int:
+        """Reserve a free slot for ``ids`` (host only: the slot's device record stays inactive until its
+        prompt is prefilled, so ``step`` skips it) and return it; ``prefill`` does the work."""
+        m = self.m
+        if not m.prefill_kernel:
+            raise ValueError(f"head dim {m.cfg.head_dim}: the batched prefill needs 64 or 128 (use admit)")
+        free = [b for b, p in enumerate(self.pos) if p is None and b not in self.pend]
+        if not free:
+            raise RuntimeError(f"all {self.S} sequence slots are in use")
+        if not ids or len(ids) >= m.cfg.n_ctx:
+            raise ValueError(f"a prompt of {len(ids)} tokens leaves no room in a context of {m.cfg.n_ctx}")
+        sd = self.seed if seed is None else int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.pend[free[0]] = [list(ids), 0, sd]
+        return free[0]
+
+    def _prefill_ws(self, chunk: int) -> dict:
+        """The pass's workspaces for S * chunk packed rows, allocated once (again only for a larger chunk)."""
+        rows = (self.S * chunk + self.PF_ROWS - 1) // self.PF_ROWS * self.PF_ROWS
+        w = self._pf
+        if w is not None and w["rows"] >= rows:
+            return w
+        cfg, dev = self.m.cfg, self.m.device
+        kvd = cfg.kv_heads * cfg.head_dim
+        z = lambda r, n, dt=torch.bfloat16: torch.zeros((r, n), dtype=dt, device=dev)  # noqa: E731
+        w = {"rows": rows, "x": z(rows, cfg.d), "xb": z(rows, cfg.d), "h": z(rows, cfg.d),
+             "qkv": z(rows, cfg.d + 2 * kvd), "attn": z(rows, cfg.d), "ffn": z(rows, cfg.ffn),
+             "last": z(self.PF_ROWS, cfg.d), "hl": z(self.PF_ROWS, cfg.d),
+             "lg": z(self.PF_ROWS, self.m.head.shape[0], torch.float32),
+             "ids": torch.zeros(rows, dtype=torch.int64, device=dev),
+             "ids_host": torch.zeros(rows, dtype=torch.int64).pin_memory(),
+             "sel": torch.zeros(self.S, dtype=torch.int64, device=dev),
+             "sel_host": torch.zeros(self.S, dtype=torch.int64).pin_memory()}
+        self._pf = w
+        return w
+
+    def _dense(self, w):
+        """The bf16 matrix the MFMA GEMM reads: a 4- / 8-bit one is dequantised into the model's scratch."""
+        if not isinstance(w, Q4Weight):
+            return w
+        m = self.m
+        n_el = w.shape[0] * w.shape[1]
+        if m._q4_scratch is None or m._q4_scratch.numel() < n_el:
+            m._q4_scratch = torch.empty(n_el, dtype=torch.bfloat16, device=m.device)
+        return w.dequant(m.L, m._q4_scratch[:n_el].view(w.shape))
+
+    def _pf_mm(self, mode, x, M, w, res, out, what):
+        """out[:M] = epilogue(x[:M] @ w^T) on nomic_gemm; x / res / out are workspace row blocks."""
+        from .nomic import _chk, _stream
+        wd = self._dense(w)
+        N, K = wd.shape
+        rp, ldr = (res.data_ptr(), res.stride(0)) if res is not None else (None, 0)
+        _chk(self.m.L.nomic_gemm(mode, x.data_ptr(), x.stride(0), wd.data_ptr(), K, M, N, K, out.data_ptr(),
+                                 out.stride(0), rp, ldr, None, None, 0, _stream()), what)
+
+    @torch.no_grad()
+    def prefill(self, chunk: int) -> Dict[int, int]:
+        """ONE pass over the next ``min(chunk, remaining)`` prompt tokens of every pending slot (at most
+        S * chunk packed rows): {slot: first token} for the prompts that end in this pass, which are live
+        from here on.  Call it until ``pending()`` is empty; between two passes the live slots may ``step``."""
+        from .nomic import _chk, _stream
+        chunk = int(chunk)
+        if chunk < 1:
+            raise ValueError(f"chunk must be >= 1, not {chunk}")
+        if not self.pend:
+            return {}
+        m, cfg, L, S = self.m, self.m.cfg, self.m.L, self.S
+        H, KVH, hd = cfg.heads, cfg.kv_heads, cfg.head_dim
+        w = self._prefill_ws(chunk)
+        segs, toks, ends = [], [], []
+        for slot in sorted(self.pend):
+            ids, off, _ = self.pend[slot]
+            n = min(chunk, len(ids) - off)
+            if off + n == len(ids):
+                ends.append((slot, len(toks) + n - 1))
+            segs.append((len(toks), n, off, slot))
+            toks += ids[off: off + n]
+        T = len(toks)
+        Tp = (T + self.PF_ROWS - 1) // self.PF_ROWS * self.PF_ROWS
+        table = np.ascontiguousarray(np.array(segs, dtype=np.int32))  # host {row0, n, pos0, slot}, read at launch
+        tp, ns = table.ctypes.data, len(segs)
+        s = _stream()
+        x, xb, h, qkv, attn, ffn = w["x"], w["xb"], w["h"], w["qkv"], w["attn"], w["ffn"]
+        w["ids_host"][:T] = torch.tensor(toks, dtype=torch.int64)
+        w["ids"][:T].copy_(w["ids_host"][:T], non_blocking=True)
+        torch.index_select(m.emb, 0, w["ids"][:T], out=x[:T])  # packed once ...
+        x[T:Tp].zero_()                                         # ... and padded once, to the GEMM's row multiple
+
+        def rms(src, wt, dst, rows):
+            _chk(L.dec_rmsnorm(src.data_ptr(), src.stride(0), wt.data_ptr(), rows, cfg.d, cfg.eps, dst.data_ptr(),
+                               dst.stride(0), s), "rmsnorm")
+
+        # one GEMM kernel for every pass: the automatic choice moves with the rows of a pass, and a request's
+        # bits must not (the 128 x 128 kernel's row results depend on neither M nor the row's place)
+        prev = L.nomic_gemm_set_variant(128)
+        try:
+            for li, lw in enumerate(m.layers):
+                rms(x, lw["n1"], h, T)
+                self._pf_mm(0, h, T, lw["qkv"], None, qkv, "gemm qkv")
+                kc, vc = self.kv[0, li, 0], self.kv[0, li, 1]
+                _chk(L.dec_rope_kv_seg(qkv.data_ptr(), qkv.stride(0), T, tp, ns, H, KVH, hd, m.cos.data_ptr(),
+                                       m.sin.data_ptr(), kc.data_ptr(), vc.data_ptr(), KVH * hd, self.kv.stride(0),
+                                       S, cfg.n_ctx, s), "rope_kv_seg")
+                _chk(L.dec_attn_prefill_kv_seg(qkv.data_ptr(), qkv.stride(0), T, tp, ns, kc.data_ptr(), vc.data_ptr(),
+                                               KVH * hd, self.kv.stride(0), S, cfg.n_ctx, H, KVH, hd, hd ** -0.5,
+                                               attn.data_ptr(), attn.stride(0), s), "attn_prefill_kv_seg")
+                self._pf_mm(1, attn, T, lw["o"], x, xb, "gemm o")
+                rms(xb, lw["n2"], h, T)
+                self._pf_mm(2, h, T, lw["ug"], None, ffn, "gemm up|gate")
+                self._pf_mm(1, ffn, T, lw["down"], xb, x, "gemm down")
+            if ends:  # only the last rows of the prompts that end here see the final norm and the LM head
+                k = len(ends)
+                w["sel_host"][:k] = torch.tensor([r for _, r in ends], dtype=torch.int64)
+                w["sel"][:k].copy_(w["sel_host"][:k], non_blocking=True)
+                torch.index_select(x, 0, w["sel"][:k], out=w["last"][:k])
+                rms(w["last"], m.norm_out, w["hl"], k)
+                self._pf_mm(4, w["hl"], k, m.head, None, w["lg"], "gemm head")
+        finally:
+            L.nomic_gemm_set_variant(prev)
+        for slot in list(self.pend):
+            self.pend[slot][1] += min(chunk, len(self.pend[slot][0]) - self.pend[slot][1])
+        out = {}
+        for i, (slot, _) in enumerate(ends):
+            ids, _, sd = self.pend[slot]
+            self._write_state(slot, [len(ids), 0, 0, 1, sd & 0xFFFFFFFF, sd >> 32, 0, 0])
+            self.logits[slot, : cfg.vocab].copy_(w["lg"][i, : cfg.vocab])
+            self._sample(slot, 1, inc_pos=0)
+        torch.cuda.current_stream().synchronize()
+        for slot, _ in ends:
+            self.pos[slot] = len(self.pend.pop(slot)[0])
+            out[slot] = int(self.host_tok[slot])
+        self.prefill_passes += 1
+        return out
 
     # ----------------------------------------------------------------- step --
     def _sample(self, slot0: int, n: int, inc_pos: int):
