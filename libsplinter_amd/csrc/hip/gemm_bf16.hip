@@ -21,6 +21,7 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "gemm_tile.hpp"
 #include "glds_asm.hpp"
 #include "nomic_api.h"
 
@@ -65,19 +66,7 @@ __device__ __forceinline__ bf16x8 lds_frag(const char* tile, int r, int c) {
   return *(const bf16x8*)(tile + r * 128 + ((c ^ (r & 7)) << 4));
 }
 
-__device__ __forceinline__ void remap_tile(int bid, int nb, int nt, int gn, int& mt, int& ntile) {
-  // bijective XCD remap: blocks b and b+8 share an XCD; give each XCD a
-  // contiguous range of the linear tile order.  The linear order is
-  // band-major: bands of `gn` n-tiles, m-major inside a band, so the ~32
-  // tiles an XCD runs at once cover (32/gn) A row-blocks x gn W column-blocks
-  // and both fit its 4 MB L2 (gn = nt: plain row-major).
-  const int xcd = bid & 7, q = nb >> 3, r = nb & 7;
-  const int wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  const int per_band = (nb / nt) * gn;
-  const int band = wg / per_band, rem = wg - band * per_band;
-  mt = rem / gn;
-  ntile = band * gn + (rem - mt * gn);
-}
+using spl::remap_tile;  // gemm_tile.hpp
 
 struct EpiArgs {
   uint16_t* out;
@@ -133,11 +122,7 @@ __device__ __forceinline__ void load8f(const float* p, float (&o)[8]) {  // p: 3
   o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
 }
 
-// up * silu(g) with a hardware reciprocal and exp2 (v_rcp_f32 + v_exp_f32: no IEEE division
-// sequence in the epilogue; ~1 ulp, far below the bf16 output rounding)
-__device__ __forceinline__ float swiglu(float up, float g) {
-  return up * g * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-g * 1.4426950408889634f));
-}
+using spl::swiglu;  // gemm_tile.hpp
 
 template <int MODE>
 __global__ __launch_bounds__(kThreads, 2) void k_gemm_nt(const uint16_t* __restrict__ A, long lda,
@@ -838,7 +823,8 @@ void allow_lds(F* f, int bytes) {
   (void)hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
 }
 
-// Kernel choice (NOMIC_GEMM): 0 = auto, 128 = the 128^2 kernel, 256 = the 256^2 kernel.
+// Kernel choice (NOMIC_GEMM): 0 = auto, 128 = the 128^2 kernel, 256 = the 256^2 kernel, 384 = the
+// 256x384 register-epilogue kernel (gemm384.hip; STORE / SWIGLU / ROPE with N % 384 == 0).
 //
 // Measured and removed (SwiGLU shape, M = 32768, unless said otherwise):
 //   - persistent / stream-K 256^2 kernel (512-515) and the persistent register-epilogue kernel
@@ -861,7 +847,7 @@ int gemm_variant() {
   if (g_variant < 0) {
     const char* e = getenv("NOMIC_GEMM");
     const int v = e ? atoi(e) : 0;
-    g_variant = v == 128 || v == 256 ? v : 0;
+    g_variant = v == 128 || v == 256 || v == 384 ? v : 0;
   }
   return g_variant;
 }
@@ -880,13 +866,39 @@ int band_width(int ntiles, int cap) {
   return 1;
 }
 
+// The 256x384 kernel (gemm384.hip).  n-band of its tile order: 4 (3 at 6 n-tiles); the sweep is flat,
+// SwiGLU 269.6 / 266.6 / 265.9 / 266.5 / 268.2 us at 1 / 2 / 4 / 8 / 16, qkv 121.8 / 120.6 / 120.6 /
+// 120.2 us at 1 / 2 / 3 / 6 (profiles/gemm384).  Auto rule: the SwiGLU and RoPE modes (the two shapes
+// measured) from one whole round of tiles on.  us on 384 / 256^2 / 128^2, K = 768:
+//   tokens   SwiGLU (N 6144)            tiles   qkv (N 2304)               tiles
+//   32768    267.2 / 300.2 /   -        2048    114.2 / 132.0 /   -         768
+//   25000    214.0 / 237.6 / 248.1      1568    110.8 / 109.5 / 111.1       588   (auto ran 128^2: equal)
+//    8192     70.2 /  84.1 /  89.2       512     41.5 /  48.7 /  43.4       192   (below a round: stays)
+//    4096     40.6 /  44.9 /  49.0       256     36.1 /  30.7 /  28.6        96
+//    2048     32.3 /  27.3 /  25.9       128     33.9 /  17.8 /  17.1        48
+// Measured and removed: a ring of 4 W + 3 A stages (144 KB) ran 280.6 against 267.2 us (SwiGLU) and
+// 122.0 against 114.2 us (qkv) at 32768 tokens.
+constexpr int kBand384 = 4;
+bool auto384(int mode, long M, int N) {
+  if ((mode != NOMIC_EPI_SWIGLU && mode != NOMIC_EPI_ROPE) || N % spl::kGemm384BN) return false;
+  return (M + spl::kGemm384BM - 1) / spl::kGemm384BM * (N / spl::kGemm384BN) >= num_cus();
+}
+
 template <int MODE>
 int launch(const uint16_t* A, long lda, const uint16_t* W, long ldw, long M, int N, int K, EpiArgs ep,
            hipStream_t s) {
+  // the 256x384 kernel (K in steps of 32): forced by 384; auto takes it per shape (auto384)
+  const int var = gemm_variant();
+  if constexpr (MODE == NOMIC_EPI_STORE || MODE == NOMIC_EPI_SWIGLU || MODE == NOMIC_EPI_ROPE) {
+    const int nt384 = N / spl::kGemm384BN;
+    if ((var == 384 || (var == 0 && auto384(MODE, M, N))) &&
+        spl::gemm384_ok(MODE, ep.out, ep.ldo, lda, ldw, M, N, K, ep.rope))
+      return spl::gemm384_launch(MODE, A, lda, W, ldw, M, N, K, ep.out, ep.ldo, ep.rope, ep.pos, ep.rope_cols,
+                                 band_width(nt384, kBand384), s);
+  }
   if (K % BK || N % BN || M <= 0) return (int)hipErrorInvalidValue;
   const long mpad = (M + 255) / 256 * 256;
   const bool fits = N % 256 == 0 && mpad * lda < (1L << 31) && (long)N * ldw < (1L << 31);
-  const int var = gemm_variant();
   // the 256^2 kernel runs 1 block/CU with a serial prologue / epilogue per tile: it wins once there
   // are several waves of tiles.  From 1024 tiles: the qkv projection at 32768 tokens (1152 tiles)
   // measured 137.4 us on it against 144.5 us on the 128^2 kernel (round-3 trace); the SwiGLU GEMM
@@ -924,7 +936,7 @@ int launch(const uint16_t* A, long lda, const uint16_t* W, long ldw, long M, int
 
 extern "C" int nomic_gemm_set_variant(int variant) {
   const int prev = gemm_variant();
-  g_variant = variant == 128 || variant == 256 ? variant : 0;
+  g_variant = variant == 128 || variant == 256 || variant == 384 ? variant : 0;
   return prev;
 }
 

@@ -42,9 +42,10 @@ int nomic_gemm_ln(int mode, const void *A, long lda, const void *W, long ldw, lo
                   const void *ln_g, const void *ln_b, float *part, hipStream_t stream);
 /* combine nparts (mean, M2) partials of 128 columns each into (mean, 1/sqrt(var + eps)) per row */
 int nomic_row_stats(const float *part, int nparts, long M, float eps, float *st, hipStream_t stream);
-/* GEMM kernel selection: 0 = auto, 512 = persistent 256x256 kernel with register
- * epilogue, 256 = launch-per-tile 256x256 phased kernel, 128 = 128x128 (where the
- * shape allows; otherwise the next one that does).  Returns the previous setting. */
+/* GEMM kernel selection: 0 = auto, 384 = 256x384 register-epilogue kernel (STORE / SWIGLU / ROPE,
+ * N a multiple of 384, K a multiple of 32 and >= 64, 16-B aligned output rows), 256 = launch-per-tile
+ * 256x256 phased kernel, 128 = 128x128 (where the shape allows; otherwise the next one that does).
+ * Returns the previous setting. */
 int nomic_gemm_set_variant(int variant);
 /* Tail split of the 256x256 kernel (default on; env NOMIC_GEMM_TAIL_SPLIT=0 turns it off): when the
  * last round of the grid would fill at most half the CUs (0 < tiles % CUs <= CUs / 2), its tiles
