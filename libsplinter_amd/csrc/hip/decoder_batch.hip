@@ -11,6 +11,8 @@
 //                            k_embed_tok, k_rope_kv, the four decode-attention kernels and both sampler
 //                            forms with a slot index: each slot reads its position, token, draw index
 //                            and seed from its own state record
+//   dec_rope_kv_seg          RoPE + cache append of a batched prefill pass, one segment per prompt chunk
+//   dec_kv_rows_fanout       the K / V rows of a shared prompt prefix, one source to up to 16 cache slots
 //
 // Device state: int32 st[nseq][8] = {pos, token, step, active, seed lo, seed hi, 0, 0} (decoder_common.hpp).
 // A slot with active == 0 is skipped by every state-driven kernel: its cache rows, its record and its
@@ -300,6 +302,31 @@ __global__ __launch_bounds__(256) void k_rope_kv_seg(uint16_t* __restrict__ qkv,
     }
     uint16_t* dst = col < qcols ? ptr : kc + p * ldkv + (col - qcols);
     *(uint4*)dst = pack8(o);
+  }
+}
+
+// Shared prompt prefix (BatchDecodeEngine.set_prefix): the first `rows` rows of every K / V plane of one
+// source go to up to 16 cache slots.  The destination slots travel BY VALUE in the kernel arguments, as the
+// prefill segment table does.  One thread per 16-B vector of the planes x rows x kvd / 8 source vectors, in a
+// grid-stride loop: the vector is loaded once and stored to every destination from registers, so a restore
+// to 15 held slots reads the prefix once, not 15 times.
+struct FanoutDst {
+  int ndst;
+  int slot[kMaxSeqs];
+};
+
+__global__ __launch_bounds__(256) void k_kv_rows_fanout(const uint16_t* __restrict__ src, long src_plane,
+                                                        uint16_t* __restrict__ dst, long dst_plane, long seq_stride,
+                                                        int rows, int vec_row, long total, FanoutDst tb) {
+  const long per_plane = (long)rows * vec_row;
+  for (long q = blockIdx.x * (long)blockDim.x + threadIdx.x; q < total; q += (long)gridDim.x * blockDim.x) {
+    const long plane = q / per_plane;
+    const long e = (q - plane * per_plane) * 8;  // rows are contiguous: element offset inside the plane
+    const uint4 v = *(const uint4*)(src + plane * src_plane + e);
+    uint16_t* d = dst + plane * dst_plane + e;
+#pragma unroll
+    for (int j = 0; j < kMaxSeqs; ++j)
+      if (j < tb.ndst) *(uint4*)(d + (long)tb.slot[j] * seq_stride) = v;
   }
 }
 
@@ -1156,6 +1183,44 @@ int dec_rope_kv_seg(void* qkv, long ldq, long T, const int32_t* segs, int nseg, 
   if (g > 1024) g = 1024;
   hipLaunchKernelGGL(k_rope_kv_seg, dim3((unsigned)g, (unsigned)tb.nseg), dim3(256), 0, s, (uint16_t*)qkv, ldq, H, KVH,
                      hd, cos_tab, sin_tab, (uint16_t*)kc, (uint16_t*)vc, ldkv, tb);
+  return (int)hipGetLastError();
+}
+
+// The first `rows` K / V rows of `planes` planes (one per (layer, k | v): 2 * layers) from one source to ndst
+// cache slots in one launch (k_kv_rows_fanout).  Source plane j: bf16 rows [src_rows, kvd] at src + j * src_plane;
+// destination i, plane j: rows [n_ctx, kvd] at dst + slots[i] * seq_stride + j * dst_plane; strides in elements.
+// slots: HOST int32 [ndst], checked and passed by value.  Both directions of the shared prompt prefix: capture
+// is a slot's cache -> the compact buffer (one destination, nslots 1, n_ctx the buffer's rows), restore is the
+// buffer -> the held slots.  hipErrorInvalidValue and nothing launched when: ndst is not 1..16, a slot is
+// outside 0..nslots-1 or listed twice, rows < 1 or past n_ctx or src_rows, kvd % 8, planes < 1, a plane or slot
+// stride shorter than what it strides over, a base or stride off 16 B, or the source inside a destination.
+int dec_kv_rows_fanout(const void* src, long src_plane, int src_rows, void* dst, long dst_plane, long seq_stride,
+                       const int32_t* slots, int ndst, int nslots, int n_ctx, int planes, int rows, int kvd,
+                       hipStream_t s) {
+  if (!src || !dst || !slots || ndst < 1 || ndst > kMaxSeqs || nslots < 1 || planes < 1 || kvd < 8 || kvd % 8 ||
+      rows < 1 || rows > n_ctx || rows > src_rows || src_plane % 8 || dst_plane % 8 || seq_stride % 8 ||
+      src_plane < (long)src_rows * kvd || dst_plane < (long)n_ctx * kvd ||
+      (nslots > 1 && seq_stride < (long)planes * dst_plane) || ((uintptr_t)src | (uintptr_t)dst) & 15)
+    return (int)hipErrorInvalidValue;
+  FanoutDst tb{};
+  tb.ndst = ndst;
+  const long span = (long)rows * kvd;  // elements of a plane that are touched
+  const uint16_t *s0 = (const uint16_t*)src, *s1 = s0 + (planes - 1) * src_plane + span;
+  for (int i = 0; i < ndst; ++i) {
+    const int b = slots[i];
+    if (b < 0 || b >= nslots) return (int)hipErrorInvalidValue;
+    for (int j = 0; j < i; ++j)
+      if (tb.slot[j] == b) return (int)hipErrorInvalidValue;
+    const uint16_t *d0 = (const uint16_t*)dst + b * seq_stride, *d1 = d0 + (planes - 1) * dst_plane + span;
+    if (s0 < d1 && d0 < s1) return (int)hipErrorInvalidValue;
+    tb.slot[i] = b;
+  }
+  const int vec_row = kvd / 8;
+  const long total = (long)planes * rows * vec_row;
+  long g = (total + 255) / 256;
+  if (g > 2048) g = 2048;
+  hipLaunchKernelGGL(k_kv_rows_fanout, dim3((unsigned)g), dim3(256), 0, s, (const uint16_t*)src, src_plane,
+                     (uint16_t*)dst, dst_plane, seq_stride, rows, vec_row, total, tb);
   return (int)hipGetLastError();
 }
 

@@ -23,7 +23,9 @@ Extra flags: --random-init (no GGUF: random llama weights, byte vocabulary,
 printable-byte sampling), --max-tokens (cap per request), --seed, --batch N
 (GPU: up to N requests decoded together, one shared step per token; default 1), --prefill-chunk C (with
 --batch: WAITING requests are admitted together, C prompt tokens of each per pass; default 0, one whole
-prompt at a time).
+prompt at a time), --prefix-cache (with --batch and --prefill-chunk C: the cache rows of the prompt head every
+request shares, the system prompt, are computed once and copied into each later request's cache; reuse is
+floor(head tokens / C) * C tokens, so pick C no larger than the system prompt).
 """
 from __future__ import annotations
 
@@ -32,7 +34,7 @@ import os
 import signal
 import sys
 import time
-from typing import Optional
+from typing import List, Optional
 
 LABEL_WAITING = 0x1000000000000000
 LABEL_SERVICING = 0x2000000000000000
@@ -97,6 +99,20 @@ def build_prompt(system_msg: str, user_msg: str, template: Optional[str] = None)
     return out + "<user>\n" + user_msg + "\n<assistant>\n"
 
 
+def shared_prompt_prefix(tok, system_msg: str, template: Optional[str] = None) -> List[int]:
+    """The tokens every request's prompt starts with under this system prompt and template: two prompts whose
+    user messages differ from their first character, tokenised, and their longest common token prefix.  That
+    holds for every template family, gemma's included, where the system text sits inside the user turn.  It is
+    a hint only: the engine compares the ids of each request, so a request that tokenises differently at the
+    seam just misses."""
+    a = tok.encode(build_prompt(system_msg, "What is it?", template))
+    b = tok.encode(build_prompt(system_msg, "tell me more", template))
+    n = 0
+    while n < min(len(a), len(b)) and a[n] == b[n]:
+        n += 1
+    return list(a[:n])
+
+
 def is_word_boundary(piece: bytes) -> bool:
     return bool(piece) and (piece[:1] in (b" ", b"\n") or b"\n" in piece)
 
@@ -149,7 +165,7 @@ class CompletionStream:
 
 class Splainference:
     def __init__(self, store, model, tokenizer, sampler, system_prompt_key=None, max_tokens: int = 256,
-                 batch: int = 1, prefill_chunk: int = 0):
+                 batch: int = 1, prefill_chunk: int = 0, prefix_cache: bool = False):
         self.store, self.model, self.tok, self.sampler = store, model, tokenizer, sampler
         self.system_prompt_key = system_prompt_key
         self.max_tokens = max_tokens
@@ -169,6 +185,10 @@ class Splainference:
         # --prefill-chunk C: batched, chunked admission (BatchDecodeEngine.submit / prefill) where the batch
         # engine serves and the prefill kernels take the head dim; ignored wherever serving is sequential
         self.prefill_chunk = prefill_chunk if self.batch_engine is not None and model.prefill_kernel else 0
+        # --prefix-cache: BatchDecodeEngine.set_prefix with the prompt head the system prompt gives every request;
+        # it rides on the chunked admission, so it is ignored wherever --prefill-chunk is
+        self.prefix_cache = bool(prefix_cache) and self.prefill_chunk > 0
+        self._prefix_src: Optional[str] = None  # the system prompt value the engine's prefix was built from
 
     def _read_request(self, key: str):
         s = self.store
@@ -273,8 +293,10 @@ class Splainference:
         two shared steps WAITING keys are admitted into free slots (their prefill stalls the others for its
         duration; with --prefill-chunk C they are submitted instead and one pass over the next C prompt tokens
         of every submitted request runs before each step, a request's stream starting when its first token
-        arrives); after a step every request streams its own token.  A request's seed is the daemon seed XOR
-        the key's hash, so its completion does not depend on what shares its steps.  Returns requests served."""
+        arrives; with --prefix-cache the engine's shared prefix follows the system prompt key, re-read whenever
+        nothing is pending); after a step every request streams its own token.  A request's seed is the daemon
+        seed XOR the key's hash, so its completion does not depend on what shares its steps.  Returns requests
+        served."""
         eng = self.batch_engine
         live = {}  # slot -> [key, stream, t0, next token]
         pend = {}  # slot -> (key, prompt tokens, bytes written, t0): submitted, first token not drawn yet
@@ -288,6 +310,14 @@ class Splainference:
             self._done(key, t0)
 
         while True:
+            if self.prefix_cache and self.system_prompt_key and not pend:
+                v = self.store.get(self.system_prompt_key)
+                system_msg = v.decode("utf-8", "replace") if v else ""
+                if system_msg != self._prefix_src:
+                    head = shared_prompt_prefix(self.tok, system_msg, getattr(self.tok, "chat_template", None))
+                    # a head that fills the context serves no request: nothing to reuse
+                    eng.set_prefix(head if len(head) < self.model.cfg.n_ctx else None, chunk)
+                    self._prefix_src = system_msg
             if _running:
                 for key in self.waiting():
                     if len(live) + len(pend) >= eng.S or not _running:
@@ -322,6 +352,9 @@ class Splainference:
             if not live:
                 if pend:
                     continue
+                if self.prefix_cache:
+                    print(f"[splainference] prefix cache: {eng.prefix_hits} hits, {eng.prefix_rows_reused} rows "
+                          "reused", flush=True)
                 return served
             for slot in list(live):
                 if not _running or not live[slot][1].take(live[slot][3]):
@@ -353,6 +386,10 @@ def main(argv=None) -> int:
     ap.add_argument("--prefill-chunk", type=int, default=0,
                     help="with --batch on the GPU: admit WAITING requests together, C prompt tokens of each per "
                          "pass, one pass between two decode steps; 0 (default) prefills one whole prompt at a time")
+    ap.add_argument("--prefix-cache", action="store_true",
+                    help="with --batch >= 2 and --prefill-chunk C > 0: compute the cache rows of the prompt head "
+                         "every request shares (the --system-prompt-key text) once and copy them into each later "
+                         "request; floor(head / C) * C tokens are reused, so pick C no larger than the system prompt")
     ap.add_argument("--device", default=None, help="cuda (default when a GPU is present) or cpu")
     ap.add_argument("--quant", default="auto", choices=["auto", "bf16", "q4"],
                     help="weights in HBM: q4 = 4-bit Q4G32 (decode streams 0.625 B per weight), bf16, or auto "
@@ -369,6 +406,9 @@ def main(argv=None) -> int:
         return 1
     if a.prefill_chunk < 0:
         print("Error: --prefill-chunk must be >= 0.", file=sys.stderr)
+        return 1
+    if a.prefix_cache and (a.batch < 2 or a.prefill_chunk <= 0):
+        print("Error: --prefix-cache needs --batch >= 2 and --prefill-chunk > 0.", file=sys.stderr)
         return 1
     import torch
     from ..store import Store
@@ -399,7 +439,8 @@ def main(argv=None) -> int:
             model.cfg.n_ctx = min(a.n_ctx, model.cos.shape[0])
     print(f"[Startup]: context window = {model.cfg.n_ctx} tokens, {model.quant} weights.", flush=True)
     sampler = Sampler(seed=a.seed, mask=tok.printable_mask(model.cfg.vocab))
-    d = Splainference(store, model, tok, sampler, a.system_prompt_key, a.max_tokens, a.batch, a.prefill_chunk)
+    d = Splainference(store, model, tok, sampler, a.system_prompt_key, a.max_tokens, a.batch, a.prefill_chunk,
+                      a.prefix_cache)
     pending = d.waiting()
     if pending:
         print(f"[Startup]: {len(pending)} waiting key(s) found at cold start.", flush=True)

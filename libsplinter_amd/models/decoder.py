@@ -301,6 +301,10 @@ class CausalLM:
             self.L.dec_attn_prefill_kv_seg.argtypes = [P, c_long, c_long, P, c_int, P, P, c_long, c_long, c_int, c_int,
                                                        c_int, c_int, c_int, c_float, P, c_long, P]
             self.L.dec_attn_prefill_kv_seg.restype = c_int
+            # the shared prompt prefix: the destination slots are a host int32 [ndst] array
+            self.L.dec_kv_rows_fanout.argtypes = [P, c_long, c_int, P, c_long, c_long, P, c_int, c_int, c_int, c_int,
+                                                  c_int, c_int, P]
+            self.L.dec_kv_rows_fanout.restype = c_int
             self.L._dec_declared = True
 
     @classmethod
@@ -600,7 +604,16 @@ class BatchDecodeEngine:
     start, the two segment kernels never look past a segment, and every GEMM of a pass runs on the
     128 x 128 kernel, whose row results do not depend on the row count or on where a row sits: a
     request's first token, cache rows and later tokens do not depend on what shares its passes.
-    Prefill overlapped with the decode step on a second stream is out of scope."""
+    Prefill overlapped with the decode step on a second stream is out of scope.
+
+    ``set_prefix(ids, chunk)`` names a prompt prefix many requests share (a system prompt): its first
+    R = floor(len / chunk) * chunk tokens' K / V rows are computed once, by the first request that carries
+    them (the donor), copied into a compact [layers, 2, R, kvd] buffer, and copied from there into the
+    cache of every later carrying request (dec_kv_rows_fanout, one launch per pass for all of them), which
+    then starts its prefill at position R.  R is a multiple of the chunk, so such a request runs exactly
+    the passes it would have run past R anyway, over cache rows that hold the bits it would have computed:
+    no completion changes by a byte.  Only ``submit`` + ``prefill`` use the prefix; the eager ``admit`` path
+    and the single-sequence ``DecodeEngine`` always prefill the whole prompt."""
 
     ST_WORDS = 8
 
@@ -639,9 +652,17 @@ class BatchDecodeEngine:
         self.graphs = {}                      # attention span (512 or the capacity) -> captured step
         self.pos: List[Optional[int]] = [None] * S   # host mirror of each live slot's position
         self.steps = 0
-        self.pend: Dict[int, list] = {}       # pending slot -> [prompt ids, tokens prefilled, seed]
+        self.pend: Dict[int, list] = {}       # pending slot -> [prompt ids, tokens prefilled, seed, carries prefix]
         self._pf: Optional[dict] = None       # prefill workspaces, sized for S * chunk rows
         self.prefill_passes = 0
+        self.prefill_rows = 0                 # packed rows T summed over the passes
+        self.prefix_hits = 0                  # requests that started from the captured prefix rows
+        self.prefix_rows_reused = 0           # R per hit
+        self._pfx_ids: Optional[List[int]] = None     # the kept ids[:R]; None: no prefix set
+        self._pfx_chunk = 0
+        self._pfx_buf: Optional[torch.Tensor] = None  # [layers, 2, R, kvd]
+        self._pfx_ready = False               # the buffer holds the rows (a donor reached R)
+        self._pfx_donor: Optional[int] = None
 
     # ---------------------------------------------------------------- slots --
     def active(self) -> List[int]:
@@ -681,6 +702,8 @@ class BatchDecodeEngine:
         """Retire a sequence: the slot is skipped by every later step until it is admitted again."""
         if slot in self.pend:  # a pending prompt is cancelled: its record was never active
             del self.pend[slot]
+            if slot == self._pfx_donor:  # the next pass picks the lowest carrying slot, from its offset 0
+                self._pfx_donor = None
             return
         if self.pos[slot] is None:
             raise ValueError(f"slot {slot} is not in use")
@@ -710,8 +733,52 @@ class BatchDecodeEngine:
         if not ids or len(ids) >= m.cfg.n_ctx:
             raise ValueError(f"a prompt of {len(ids)} tokens leaves no room in a context of {m.cfg.n_ctx}")
         sd = self.seed if seed is None else int(seed) & 0xFFFFFFFFFFFFFFFF
-        self.pend[free[0]] = [list(ids), 0, sd]
+        ids = list(ids)
+        R = len(self._pfx_ids or ())
+        # carrying is all or nothing: the whole kept prefix, and at least one token of the request's own
+        self.pend[free[0]] = [ids, 0, sd, R > 0 and len(ids) > R and ids[:R] == self._pfx_ids]
         return free[0]
+
+    def set_prefix(self, ids: Optional[List[int]], chunk: int) -> int:
+        """Name the prompt prefix that requests share and return R = (len(ids) // chunk) * chunk, the tokens
+        whose cache rows are reused (0: nothing is).  A new prefix drops the captured rows; the next request
+        that carries it computes them again.  ``set_prefix(None, 0)`` turns the reuse off and frees the buffer.
+        RuntimeError while a request is pending: change the prefix between two admission waves."""
+        if self.pend:
+            raise RuntimeError(f"set_prefix with {len(self.pend)} pending request(s): wait until pending() is empty")
+        self._pfx_ids, self._pfx_chunk, self._pfx_buf = None, 0, None
+        self._pfx_ready, self._pfx_donor = False, None
+        if ids is None:
+            return 0
+        chunk = int(chunk)
+        if chunk < 1:
+            raise ValueError(f"chunk must be >= 1, not {chunk}")
+        cfg = self.m.cfg
+        R = len(ids) // chunk * chunk
+        if R >= cfg.n_ctx:
+            raise ValueError(f"a prefix of {R} tokens leaves no room in a context of {cfg.n_ctx}")
+        if R > 0:
+            kvd = cfg.kv_heads * cfg.head_dim
+            need = cfg.layers * 2 * R * kvd * 2
+            free = torch.cuda.mem_get_info(torch.device(self.m.device))[0]
+            if need > free:
+                raise RuntimeError(f"prefix rows for {R} tokens need {need >> 20} MiB, {free >> 20} MiB of device "
+                                   "memory are free: shorten the prefix")
+            self._pfx_buf = torch.zeros((cfg.layers, 2, R, kvd), dtype=torch.bfloat16, device=self.m.device)
+        self._pfx_ids, self._pfx_chunk = [int(t) for t in ids[:R]], chunk
+        return R
+
+    def _fanout(self, src: torch.Tensor, src_rows: int, dst: torch.Tensor, dst_rows: int, seq_stride: int,
+                slots: List[int], nslots: int, rows: int):
+        """rows [0, rows) of every (layer, k | v) plane: src [layers, 2, src_rows, ..] -> dst [.., layers, 2,
+        dst_rows, ..] of each listed slot, one launch on the current stream."""
+        from .nomic import _chk, _stream
+        cfg = self.m.cfg
+        kvd = cfg.kv_heads * cfg.head_dim
+        tb = np.ascontiguousarray(np.array(slots, dtype=np.int32))  # host array, read at launch
+        _chk(self.m.L.dec_kv_rows_fanout(src.data_ptr(), src_rows * kvd, src_rows, dst.data_ptr(), dst_rows * kvd,
+                                         seq_stride, tb.ctypes.data, len(slots), nslots, dst_rows, 2 * cfg.layers,
+                                         rows, kvd, _stream()), "kv_rows_fanout")
 
     def _prefill_ws(self, chunk: int) -> dict:
         """The pass's workspaces for S * chunk packed rows, allocated once (again only for a larger chunk)."""
@@ -761,14 +828,39 @@ class BatchDecodeEngine:
         chunk = int(chunk)
         if chunk < 1:
             raise ValueError(f"chunk must be >= 1, not {chunk}")
+        R = len(self._pfx_ids or ())
+        if R and chunk != self._pfx_chunk:
+            raise ValueError(f"chunk {chunk} under a prefix set for chunk {self._pfx_chunk}: reuse stops at a "
+                             "multiple of the chunk so that a request's passes do not move")
         if not self.pend:
             return {}
         m, cfg, L, S = self.m, self.m.cfg, self.m.L, self.S
         H, KVH, hd = cfg.heads, cfg.kv_heads, cfg.head_dim
         w = self._prefill_ws(chunk)
+        # the shared prefix: once captured, a carrying request still at offset 0 starts from copied rows (a hit);
+        # until then one carrying request (the donor) computes them and the others wait at offset 0 (held)
+        carrying = [b for b in sorted(self.pend) if self.pend[b][3]] if R else []
+        donor, held = None, ()
+        if self._pfx_ready:
+            hits = [b for b in carrying if self.pend[b][1] == 0]
+            if hits:  # one launch for every such slot of the pass, ahead of its first kernel
+                self._fanout(self._pfx_buf, R, self.kv, cfg.n_ctx, self.kv.stride(0), hits, S, R)
+                for b in hits:
+                    self.pend[b][1] = R
+                self.prefix_hits += len(hits)
+                self.prefix_rows_reused += R * len(hits)
+        elif carrying:
+            # the donor stays the donor while it is pending (a request submitted into a lower slot meanwhile is
+            # held like the rest); after its release the lowest carrying slot takes over, from its own offset 0
+            if self._pfx_donor not in carrying:
+                self._pfx_donor = carrying[0]
+            donor = self._pfx_donor
+            held = [b for b in carrying if b != donor]
         segs, toks, ends = [], [], []
         for slot in sorted(self.pend):
-            ids, off, _ = self.pend[slot]
+            if slot in held:
+                continue
+            ids, off = self.pend[slot][:2]
             n = min(chunk, len(ids) - off)
             if off + n == len(ids):
                 ends.append((slot, len(toks) + n - 1))
@@ -816,11 +908,16 @@ class BatchDecodeEngine:
                 self._pf_mm(4, w["hl"], k, m.head, None, w["lg"], "gemm head")
         finally:
             L.nomic_gemm_set_variant(prev)
-        for slot in list(self.pend):
-            self.pend[slot][1] += min(chunk, len(self.pend[slot][0]) - self.pend[slot][1])
+        for _, n, _, slot in segs:
+            self.pend[slot][1] += n
+        if donor is not None and self.pend[donor][1] >= R:
+            # the donor's rows [0, R) are final: keep them (its cache -> the buffer, behind the pass on the same
+            # stream); the prefix counts as captured from the next pass on
+            self._fanout(self.kv[donor], cfg.n_ctx, self._pfx_buf, R, 0, [0], 1, R)
+            self._pfx_ready, self._pfx_donor = True, None
         out = {}
         for i, (slot, _) in enumerate(ends):
-            ids, _, sd = self.pend[slot]
+            ids, _, sd = self.pend[slot][:3]
             self._write_state(slot, [len(ids), 0, 0, 1, sd & 0xFFFFFFFF, sd >> 32, 0, 0])
             self.logits[slot, : cfg.vocab].copy_(w["lg"][i, : cfg.vocab])
             self._sample(slot, 1, inc_pos=0)
@@ -829,6 +926,7 @@ class BatchDecodeEngine:
             self.pos[slot] = len(self.pend.pop(slot)[0])
             out[slot] = int(self.host_tok[slot])
         self.prefill_passes += 1
+        self.prefill_rows += T
         return out
 
     # ----------------------------------------------------------------- step --
