@@ -1,11 +1,13 @@
 // decoder_common.hpp — helpers shared by decoder_kernels.hip (one generation) and decoder_batch.hip
 // (up to 16 generations per step): bf16 packing, wave reductions, the device state record, the
-// sampler's workspace layout and draw, and the split-L geometry of the decode attention.
+// sampler's workspace layout and draw, the split-L geometry of the decode attention and the host's
+// shape dispatch.  The kernel bodies the two files share are in decoder_body_*.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cmath>
 #include <cstdlib>
+#include <type_traits>
 
 namespace {
 
@@ -31,6 +33,15 @@ __device__ __forceinline__ uint4 pack8(const float* f) {
 // step (decoder_batch.hip) keeps one 8-word record per sequence slot: the same three words, then
 // [3] active (0 / 1), [4] [5] the slot's sampler seed (low, high half), [6] [7] reserved (zero).
 enum { ST_POS = 0, ST_TOK = 1, ST_STEP = 2, ST_ACTIVE = 3, ST_SEED_LO = 4, ST_SEED_HI = 5, ST_WORDS = 8 };
+
+// what a sampler leaves in its record: the drawn token, pos += inc_pos, one more draw; the token also goes
+// to host_tok (pinned, may be null)
+__device__ __forceinline__ void state_commit(int32_t* st, int t, int inc_pos, int32_t* host_tok) {
+  st[ST_TOK] = t;
+  st[ST_POS] += inc_pos;
+  st[ST_STEP] += 1;
+  if (host_tok) __hip_atomic_store(host_tok, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
 
 // Batched prompt prefill (dec_rope_kv_seg, dec_attn_prefill_kv_seg): up to 16 segments of the packed token
 // matrix.  Segment i owns rows row0 .. row0 + n - 1, the tokens at absolute positions pos0 .. pos0 + n - 1
@@ -108,6 +119,32 @@ inline int decode_splits(int L) {
   if (L <= 512) return 1;
   const int sp = (L + 255) / 256;
   return sp > kMaxSplits ? kMaxSplits : sp;
+}
+
+// host dispatch: the runtime shape as compile-time constants: f(ic<D>) for d = head dim / 64 in 1..4, and
+// f(ic<D>, ic<G>) with g = heads per workgroup in {1, 2, 4, 8}
+template <int V>
+using ic = std::integral_constant<int, V>;
+
+template <class F>
+void with_d(int d, F f) {
+  switch (d) {
+    case 1: f(ic<1>{}); break;
+    case 2: f(ic<2>{}); break;
+    case 3: f(ic<3>{}); break;
+    default: f(ic<4>{}); break;
+  }
+}
+template <class F>
+void with_d_g(int d, int g, F f) {
+  with_d(d, [&](auto D) {
+    switch (g) {
+      case 2: f(D, ic<2>{}); break;
+      case 4: f(D, ic<4>{}); break;
+      case 8: f(D, ic<8>{}); break;
+      default: f(D, ic<1>{}); break;
+    }
+  });
 }
 
 // counter-based uniform in [0, 1): splitmix64 of (seed, draw index)

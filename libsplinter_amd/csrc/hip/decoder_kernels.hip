@@ -114,390 +114,45 @@ __global__ __launch_bounds__(256) void k_rope(uint16_t* __restrict__ qkv, long l
   }
 }
 
-// Single-token decode attention over the KV cache (GQA): one 1024-thread workgroup per
-// query head h (kv head h / (H/KVH)); its 16 waves take interleaved 64-key chunks (a decode
-// step launches only H workgroups, so the split-L width lives inside the workgroup).  Inside a
-// chunk each lane scores one key (16-B loads along its cache row against the LDS-resident,
-// pre-scaled q), the wave keeps an online softmax (max/sum via __shfl_xor), and the V rows
-// are accumulated with p broadcast by __shfl, each lane owning DPL = hd/64 contiguous
-// output dims.  The 16 partial (m, l, acc) states merge in LDS.  K/V are [L, ldkv] rows
-// (ldkv = KVH*hd elements) starting at the kv head's column.
+// Decode attention and the sampler: each kernel here is its signature, the prologue that names this
+// generation's operands, and a body that is one text for it and for its slot-indexed form in
+// decoder_batch.hip (decoder_body_*.hpp, where the kernels are described).  The bodies are included, not
+// called: a shared function moves the register allocation (profiles/decoder_prune/README.md), the same
+// tokens do not (profiles/decoder_share/README.md).
+
+// one 1024-thread workgroup per query head, its 16 waves over interleaved 64-key chunks
 template <int DPL>
 __global__ __launch_bounds__(kDecWaves * 64) void k_attn_decode(const uint16_t* __restrict__ q, const uint16_t* __restrict__ K,
                                                      const uint16_t* __restrict__ V, long ldkv, int L, int grp,
                                                      int hd, float scale, uint16_t* __restrict__ out,
                                                      const int32_t* __restrict__ st) {
   if (st) L = st[0] + 1;  // graph-captured decode step: the cache length lives on the device
-  const int h = blockIdx.x;
-  const int kvh = h / grp;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  __shared__ float qs[256];
-  __shared__ float wm[kDecWaves], wl[kDecWaves];
-  __shared__ float wacc[kDecWaves][256];
-  for (int d = threadIdx.x; d < hd; d += kDecWaves * 64) qs[d] = bf2f(q[(long)h * hd + d]) * scale;
-  __syncthreads();
-  const uint16_t* Kb = K + (long)kvh * hd;
-  const uint16_t* Vb = V + (long)kvh * hd + lane * DPL;
-  float m = -INFINITY, l = 0.f, acc[DPL];
-#pragma unroll
-  for (int i = 0; i < DPL; ++i) acc[i] = 0.f;
-  for (int base = wave * 64; base < L; base += kDecWaves * 64) {
-    const int j = base + lane;
-    float s = -INFINITY;
-    if (j < L) {
-      const uint16_t* kr = Kb + (long)j * ldkv;
-      // hd == 64 * DPL: the key row in batches of 8 16-B loads issued before their FMAs (a
-      // runtime-bound loop issued them one latency at a time: 28 us per step at 32 heads); one batch
-      // in flight keeps the 1024-thread block inside its 128 VGPRs
-      float dot = 0.f;
-#pragma unroll 1
-      for (int cb = 0; cb < DPL; ++cb) {
-        uint4 kv[8];
-#pragma unroll
-        for (int c = 0; c < 8; ++c) kv[c] = *(const uint4*)(kr + cb * 64 + c * 8);
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-          float f[8];
-          unpack8(kv[c], f);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) dot += f[e] * qs[cb * 64 + c * 8 + e];
-        }
-      }
-      s = dot;
-    }
-    float cm = s;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) cm = fmaxf(cm, __shfl_xor(cm, o, 64));
-    const float mn = fmaxf(m, cm);  // finite: lane 0 of every visited chunk holds a key
-    const float corr = __expf(m - mn);
-    const float p = j < L ? __expf(s - mn) : 0.f;
-    float ps = p;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) ps += __shfl_xor(ps, o, 64);
-    l = l * corr + ps;
-#pragma unroll
-    for (int i = 0; i < DPL; ++i) acc[i] *= corr;
-    const int nv = min(64, L - base);
-    for (int t = 0; t < nv; ++t) {
-      const float pt = __shfl(p, t, 64);
-      const uint16_t* vr = Vb + (long)(base + t) * ldkv;
-#pragma unroll
-      for (int i = 0; i < DPL; ++i) acc[i] += pt * bf2f(vr[i]);
-    }
-    m = mn;
-  }
-  if (lane == 0) { wm[wave] = m; wl[wave] = l; }
-#pragma unroll
-  for (int i = 0; i < DPL; ++i) wacc[wave][lane * DPL + i] = acc[i];
-  __syncthreads();
-  float M = wm[0];
-#pragma unroll
-  for (int w = 1; w < kDecWaves; ++w) M = fmaxf(M, wm[w]);
-  float c[kDecWaves], den = 0.f;
-#pragma unroll
-  for (int w = 0; w < kDecWaves; ++w) { c[w] = __expf(wm[w] - M); den += wl[w] * c[w]; }
-  const float inv = 1.f / den;
-  for (int d = threadIdx.x; d < hd; d += kDecWaves * 64) {
-    float o = 0.f;
-#pragma unroll
-    for (int w = 0; w < kDecWaves; ++w) o += wacc[w][d] * c[w];
-    o *= inv;
-    out[(long)h * hd + d] = __builtin_bit_cast(uint16_t, (__bf16)o);
-  }
+#include "decoder_body_attn_walk.hpp"
 }
 
-// k_attn_decode_g: decode attention for caches of at most kSmallL keys (the single-workgroup regime).
-// One workgroup per KV head serves its G query heads, so every K / V row is read once for the group
-// instead of once per head, and no phase walks the keys one at a time:
-//   scores  hd/8 lanes per key row (16-B pieces), U rows per lane in flight, G dot products per piece,
-//           reduced across the row's lanes with xor shuffles -> LDS sc[g][key] (q pre-scaled)
-//   softmax one wave per head: max, exp, sum over the keys in LDS
-//   P V     the same row pieces of V, U rows in flight, fp32 accumulators per (head, 8 dims), then a
-//           reduction over the 256/(hd/8) key groups through LDS.
-// k_attn_decode above walks each wave's 64 keys serially in P V (a shuffle and a
-// 4-B load per key): 28 us per layer at a 300-key cache, llama-7B heads (profiles/r3_decode_splits_short_ctx.jsonl);
-// this kernel 11.5 us, q4 decode 0.715 -> 0.577 ms/token (profiles/r3_decode_attn_small_ab.jsonl).  A 16-wave form
-// (one load round per phase, shuffle + LDS reduction) measured slower: 14.1 us (r3_decode_attn_small_wide_ab.jsonl).
-// Its split form runs the flash-decoding splits of longer caches: 3000-token prompt 0.840 -> 0.672 ms/token at 4 bits
-// (profiles/r3_decode_attn_grouped_split_ab.jsonl).
-// SPLIT: the same kernel as one split of the flash-decoding form -- workgroup (kvh, j) takes keys
-// [j * chunk, (j + 1) * chunk) (chunk <= kSmallL, the k_attn_decode_split geometry) and writes each head's
-// partial (max, sum, unnormalised P V) to ws for k_attn_combine.
+// caches of at most kSmallL keys: one workgroup per KV head serves its G query heads; SPLIT: one split of
+// the flash-decoding form
 template <int D, int G, bool SPLIT = false>
 __global__ __launch_bounds__(256) void k_attn_decode_g(const uint16_t* __restrict__ q, const uint16_t* __restrict__ K,
                                                        const uint16_t* __restrict__ V, long ldkv, int L, float scale,
                                                        uint16_t* __restrict__ out, const int32_t* __restrict__ st,
                                                        float* __restrict__ ws = nullptr) {
-  constexpr int hd = 64 * D, TPK = hd / 8, KP = 256 / TPK, U = 8;
-  static_assert(64 % TPK == 0, "a key row's lanes must sit in one wave");
   if (st) L = st[0] + 1;
-  int k0 = 0, k1 = L < kSmallL ? L : kSmallL;  // one workgroup: the host picks it only for capacities <= kSmallL
-  if constexpr (SPLIT) {
-    const int S = gridDim.y, chunk = ((L + S - 1) / S + 63) / 64 * 64;
-    k0 = blockIdx.y * chunk;
-    k1 = min(L, k0 + min(chunk, kSmallL));  // the host guarantees chunk <= kSmallL
-  }
-  const int n = k1 > k0 ? k1 - k0 : 0;
-  const int kvh = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int sub = tid % TPK, kg = tid / TPK;
-  __shared__ float sc[G][kSmallL];
-  __shared__ float red[KP][G][hd];
-  __shared__ float lsum[G], lmax[G];
-  float qv[G][8];
-#pragma unroll
-  for (int g = 0; g < G; ++g) {
-    float f[8];
-    unpack8(*(const uint4*)(q + (long)(kvh * G + g) * hd + sub * 8), f);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) qv[g][e] = f[e] * scale;
-  }
-  const uint16_t* Kb = K + (long)kvh * hd + sub * 8 + (long)k0 * ldkv;
-  const uint16_t* Vb = V + (long)kvh * hd + sub * 8 + (long)k0 * ldkv;
-  // ---- scores
-  for (int j0 = 0; j0 < n; j0 += KP * U) {
-    uint4 r[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int j = j0 + u * KP + kg;
-      r[u] = j < n ? *(const uint4*)(Kb + (long)j * ldkv) : make_uint4(0, 0, 0, 0);
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int j = j0 + u * KP + kg;
-      float f[8], d[G];
-      unpack8(r[u], f);
-#pragma unroll
-      for (int g = 0; g < G; ++g) {
-        d[g] = 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) d[g] = fmaf(f[e], qv[g][e], d[g]);
-#pragma unroll
-        for (int o = TPK / 2; o >= 1; o >>= 1) d[g] += __shfl_xor(d[g], o, 64);
-      }
-      if (sub == 0 && j < n) {
-#pragma unroll
-        for (int g = 0; g < G; ++g) sc[g][j] = d[g];
-      }
-    }
-  }
-  __syncthreads();
-  // ---- softmax, one wave per head
-  for (int g = wave; g < G; g += 4) {
-    float mx = -INFINITY;
-    for (int j = lane; j < n; j += 64) mx = fmaxf(mx, sc[g][j]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-    float sum = 0.f;
-    for (int j = lane; j < n; j += 64) {
-      const float p = __expf(sc[g][j] - mx);
-      sc[g][j] = p;
-      sum += p;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
-    if (lane == 0) {
-      lsum[g] = sum;
-      lmax[g] = mx;
-    }
-  }
-  __syncthreads();
-  // ---- P V
-  float acc[G][8];
-#pragma unroll
-  for (int g = 0; g < G; ++g)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) acc[g][e] = 0.f;
-  for (int j0 = 0; j0 < n; j0 += KP * U) {
-    uint4 r[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int j = j0 + u * KP + kg;
-      r[u] = j < n ? *(const uint4*)(Vb + (long)j * ldkv) : make_uint4(0, 0, 0, 0);
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int j = j0 + u * KP + kg;
-      if (j < n) {
-        float f[8];
-        unpack8(r[u], f);
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-          const float p = sc[g][j];
-#pragma unroll
-          for (int e = 0; e < 8; ++e) acc[g][e] = fmaf(p, f[e], acc[g][e]);
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int g = 0; g < G; ++g)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) red[kg][g][sub * 8 + e] = acc[g][e];
-  __syncthreads();
-  if constexpr (SPLIT) {
-    // ws[head][split][hd + 2] = (max, sum, unnormalised P V): the k_attn_decode_split layout; an empty split
-    // leaves max = -inf, sum 0 (k_attn_combine gives it weight 0)
-    const int S = gridDim.y;
-    for (int idx = tid; idx < G * (hd + 2); idx += 256) {
-      const int g = idx / (hd + 2), c = idx - g * (hd + 2);
-      float v;
-      if (c == 0) v = n ? lmax[g] : -INFINITY;
-      else if (c == 1) v = n ? lsum[g] : 0.f;
-      else {
-        v = 0.f;
-#pragma unroll 8
-        for (int k = 0; k < KP; ++k) v += red[k][g][c - 2];
-      }
-      ws[((long)(kvh * G + g) * S + blockIdx.y) * (hd + 2) + c] = v;
-    }
-  } else {
-    for (int idx = tid; idx < G * hd; idx += 256) {
-      const int g = idx / hd, d = idx - g * hd;
-      float o = 0.f;
-#pragma unroll 8
-      for (int k = 0; k < KP; ++k) o += red[k][g][d];
-      out[(long)(kvh * G + g) * hd + d] = __builtin_bit_cast(uint16_t, (__bf16)(o / lsum[g]));
-    }
-  }
+#include "decoder_body_attn_g.hpp"
 }
 
-// Split-L decode attention (flash-decoding) for long caches: grid (H, S), workgroup (h, j) of 4 waves
-// scores keys [j c, (j + 1) c) with c = ceil(L / S) rounded up to 64 and writes its unnormalised
-// partial (m, l, acc[hd]) to ws; k_attn_combine merges the S partials of a head.  One workgroup per
-// head streams the whole cache through one CU (164 GB/s at L = 8192, profiles/r2_decode_q4.md).
-// The chunk walk is k_attn_decode's, written out again on purpose: moved into one inlined function,
-// even word for word, it allocates other registers in 8 of the 20 kernels
-// (profiles/decoder_prune/README.md).
+// split-L (flash-decoding) for long caches: grid (H / G, S), partials to ws for k_attn_combine
 template <int DPL, int G>
 __global__ __launch_bounds__(kSplitWaves * 64) void k_attn_decode_split(
     const uint16_t* __restrict__ q, const uint16_t* __restrict__ K, const uint16_t* __restrict__ V, long ldkv, int L,
     int grp, float scale, float* __restrict__ ws, const int32_t* __restrict__ st) {
-  // G query heads of one kv group per workgroup (grouped-query attention): every key and value row
-  // is loaded once for all G heads instead of once per head
-  constexpr int hd = 64 * DPL;
   if (st) L = st[0] + 1;
-  const int h0 = blockIdx.x * G, S = gridDim.y, j = blockIdx.y;
-  const int kvh = h0 / grp;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int chunk = ((L + S - 1) / S + 63) / 64 * 64;
-  const int k0 = j * chunk, k1 = min(L, k0 + chunk);
-  __shared__ float qs[G][hd];
-  __shared__ float wm[kSplitWaves][G], wl[kSplitWaves][G];
-  __shared__ float wacc[kSplitWaves][G][hd];
-  for (int d = threadIdx.x; d < G * hd; d += kSplitWaves * 64) qs[d / hd][d % hd] = bf2f(q[(long)h0 * hd + d]) * scale;
-  __syncthreads();
-  const uint16_t* Kb = K + (long)kvh * hd;
-  const uint16_t* Vb = V + (long)kvh * hd + lane * DPL;
-  float m[G], l[G], acc[G][DPL];
-#pragma unroll
-  for (int g = 0; g < G; ++g) {
-    m[g] = -INFINITY;
-    l[g] = 0.f;
-#pragma unroll
-    for (int i = 0; i < DPL; ++i) acc[g][i] = 0.f;
-  }
-  for (int base = k0 + wave * 64; base < k1; base += kSplitWaves * 64) {
-    const int jj = base + lane;
-    float sc[G];
-#pragma unroll
-    for (int g = 0; g < G; ++g) sc[g] = -INFINITY;
-    if (jj < k1) {
-      const uint16_t* kr = Kb + (long)jj * ldkv;
-      float dot[G];
-#pragma unroll
-      for (int g = 0; g < G; ++g) dot[g] = 0.f;
-#pragma unroll 1
-      for (int cb = 0; cb < DPL; ++cb) {
-        uint4 kv[8];
-#pragma unroll
-        for (int c = 0; c < 8; ++c) kv[c] = *(const uint4*)(kr + cb * 64 + c * 8);
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-          float f[8];
-          unpack8(kv[c], f);
-#pragma unroll
-          for (int g = 0; g < G; ++g)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) dot[g] += f[e] * qs[g][cb * 64 + c * 8 + e];
-        }
-      }
-#pragma unroll
-      for (int g = 0; g < G; ++g) sc[g] = dot[g];
-    }
-    float p[G];
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-      float cm = sc[g];
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) cm = fmaxf(cm, __shfl_xor(cm, o, 64));
-      const float mn = fmaxf(m[g], cm);
-      const float corr = __expf(m[g] - mn);
-      p[g] = jj < k1 ? __expf(sc[g] - mn) : 0.f;
-      float ps = p[g];
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) ps += __shfl_xor(ps, o, 64);
-      l[g] = l[g] * corr + ps;
-#pragma unroll
-      for (int i = 0; i < DPL; ++i) acc[g][i] *= corr;
-      m[g] = mn;
-    }
-    const int nv = min(64, k1 - base);
-    for (int t = 0; t < nv; ++t) {
-      const uint16_t* vr = Vb + (long)(base + t) * ldkv;
-      float vv[DPL];
-#pragma unroll
-      for (int i = 0; i < DPL; ++i) vv[i] = bf2f(vr[i]);
-#pragma unroll
-      for (int g = 0; g < G; ++g) {
-        const float pt = __shfl(p[g], t, 64);
-#pragma unroll
-        for (int i = 0; i < DPL; ++i) acc[g][i] += pt * vv[i];
-      }
-    }
-  }
-#pragma unroll
-  for (int g = 0; g < G; ++g) {
-    if (lane == 0) { wm[wave][g] = m[g]; wl[wave][g] = l[g]; }
-#pragma unroll
-    for (int i = 0; i < DPL; ++i) wacc[wave][g][lane * DPL + i] = acc[g][i];
-  }
-  __syncthreads();
-  for (int g = 0; g < G; ++g) {
-    float M = wm[0][g];
-#pragma unroll
-    for (int w = 1; w < kSplitWaves; ++w) M = fmaxf(M, wm[w][g]);
-    float* o = ws + ((long)(h0 + g) * S + j) * (hd + 2);
-    float c[kSplitWaves], den = 0.f;
-#pragma unroll
-    for (int w = 0; w < kSplitWaves; ++w) {
-      c[w] = wm[w][g] == -INFINITY ? 0.f : __expf(wm[w][g] - M);  // an empty wave (or split) adds nothing
-      den += wl[w][g] * c[w];
-    }
-    for (int d = threadIdx.x; d < hd; d += kSplitWaves * 64) {
-      float a = 0.f;
-#pragma unroll
-      for (int w = 0; w < kSplitWaves; ++w) a += wacc[w][g][d] * c[w];
-      o[2 + d] = a;
-    }
-    if (threadIdx.x == 0) { o[0] = M; o[1] = den; }
-  }
+#include "decoder_body_attn_split.hpp"
 }
 
-// out[h] = sum_j acc_j e^(m_j - M) / sum_j l_j e^(m_j - M) over the S partials of head h
+// merges the S partials of head h
 __global__ void k_attn_combine(const float* __restrict__ ws, int S, int hd, uint16_t* __restrict__ out) {
-  const int h = blockIdx.x;
-  const float* p = ws + (long)h * S * (hd + 2);
-  float M = -INFINITY;
-  for (int j = 0; j < S; ++j) M = fmaxf(M, p[(long)j * (hd + 2)]);
-  float den = 0.f, a = 0.f;
-  const int d = threadIdx.x;
-  for (int j = 0; j < S; ++j) {
-    const float* pj = p + (long)j * (hd + 2);
-    const float c = pj[0] == -INFINITY ? 0.f : __expf(pj[0] - M);
-    den += pj[1] * c;
-    if (d < hd) a += pj[2 + d] * c;
-  }
-  if (d < hd) out[(long)h * hd + d] = __builtin_bit_cast(uint16_t, (__bf16)(a / den));
+#include "decoder_body_attn_combine.hpp"
 }
 
 // ------------------------------------------------------------------ decode step --
@@ -904,165 +559,20 @@ __global__ void k_embed_tok(const uint16_t* __restrict__ emb, int d, const int32
   for (int c = threadIdx.x; c < d / 8; c += blockDim.x) *(uint4*)(x + c * 8) = *(const uint4*)(emb + t * d + c * 8);
 }
 
-// RoPE of the step's q (in place) and k at position state.pos, and the k / v rows appended to the
-// layer's KV cache (row pos of [n_ctx, ldkv]).  One thread per rotation pair / per 8 v elements.
+// RoPE of the step's q (in place) and k at position state.pos, k / v appended to the layer's KV cache
 __global__ void k_rope_kv(uint16_t* __restrict__ qkv, int H, int KVH, int hd, const float* __restrict__ cs,
                           const float* __restrict__ sn, const int32_t* __restrict__ st, uint16_t* __restrict__ kc,
                           uint16_t* __restrict__ vc, long ldkv) {
   const long p = st[ST_POS];
-  const int half = hd >> 1;
-  const int npairs = (H + KVH) * half;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < npairs + KVH * hd; i += gridDim.x * blockDim.x) {
-    if (i < npairs) {
-      const int head = i / half, j = i - head * half;
-      uint16_t* ptr = qkv + (long)head * hd + 2 * j;
-      const float a = bf2f(ptr[0]), b = bf2f(ptr[1]);
-      const float c = cs[p * half + j], s = sn[p * half + j];
-      const uint16_t y0 = __builtin_bit_cast(uint16_t, (__bf16)(a * c - b * s));
-      const uint16_t y1 = __builtin_bit_cast(uint16_t, (__bf16)(a * s + b * c));
-      if (head < H) {
-        ptr[0] = y0;
-        ptr[1] = y1;
-      } else {
-        uint16_t* kr = kc + p * ldkv + (long)(head - H) * hd + 2 * j;
-        kr[0] = y0;
-        kr[1] = y1;
-      }
-    } else {
-      const int e = i - npairs;
-      vc[p * ldkv + e] = qkv[(long)(H + KVH) * hd + e];
-    }
-  }
+#include "decoder_body_rope_kv.hpp"
 }
 
-// top-p -> temperature -> categorical draw on the device (the reference's llama sampler chain,
-// splainference.cpp:272-279): the nucleus is the smallest set of the most probable tokens whose
-// probability reaches top_p, found as a logit threshold (no sort); the kept logits are divided by
-// temp and one token is drawn by an inclusive scan over the threads' masses.  Writes state.token
-// (and pos += inc_pos, step += 1) and the token to `host_tok` (pinned, may be null).
-// One 1024-thread workgroup with the vocabulary held in registers (V <= 1024 * kSampRegs): thread t
-// owns tokens t + 1024 k and every pass reads them from VGPRs; the categorical draw walks the
-// threads' masses in that fixed order, an equally valid order of the same distribution.
-// Nucleus threshold: the largest logit cut whose kept mass reaches top_p, found by two levels of a
-// 1024-bin mass histogram over the current interval [lo, hi) (LDS float atomics), each level keeping
-// the bin where the suffix mass crosses top_p * Z: a resolution of 40 / 2^20 (a few float ulps of a
-// logit) instead of one pass per bisection step.  Every bin has 8 copies, picked by lane & 7: flat
-// logits (a random-init model: every logit in one or two bins) put a wave's 64 same-address LDS
-// atomics into one 64-way conflict; the copies cut it to 8-way (profiles/r2_decode_q4.md).
-// Measured and removed: the same sampler reading the logits from global memory in every pass
-// (k_sample, any V) and this one at 32 registers per thread (V <= 32768), both behind dec_sample,
-// which only a test called: 255-275 us at V = 128256 and 61-65 us at V = 32000 against 53 and
-// 47 us for the k_sb_* chain (profiles/r2_decode_q4.md).
+// top-p -> temperature -> categorical draw on the device, the vocabulary in registers (V <= 1024 * kSampRegs)
 __global__ __launch_bounds__(kSampThreads) void k_sample_reg(const float* __restrict__ logits, int V,
                                                              const uint8_t* __restrict__ mask, float top_p,
                                                              float temp, uint64_t seed, int32_t* __restrict__ st,
                                                              int inc_pos, int32_t* host_tok) {
-  __shared__ float sh[kSampThreads / 64];
-  __shared__ float scan[kSampThreads];
-  __shared__ float hist[kSampThreads];
-  __shared__ float hist8[kSampThreads * 8];
-  __shared__ int jstar, pick;
-  const int tid = threadIdx.x;
-  constexpr int R = kSampRegs;
-  float v[R];
-  float m = -INFINITY;
-#pragma unroll
-  for (int k = 0; k < R; ++k) {
-    const int i = tid + k * kSampThreads;
-    v[k] = (i < V && !(mask && !mask[i])) ? logits[i] : -INFINITY;
-    m = fmaxf(m, v[k]);
-  }
-  const float M = block_reduce(m, sh, true);
-  float z = 0.f;
-#pragma unroll
-  for (int k = 0; k < R; ++k) z += __expf(v[k] - M);
-  const float Z = block_reduce(z, sh, false);
-  float lo = M - 40.f;  // nucleus cut: two levels of the replicated 1024-bin histogram; mass below M - 40 is < V e^-40
-  if (top_p < 1.f) {
-    const float target = top_p * Z;
-    float w = 40.f / kSampThreads * (1.f + 1e-6f);
-    float above = 0.f;
-    for (int level = 0; level < 2; ++level) {
-#pragma unroll
-      for (int c = 0; c < 8; ++c) hist8[c * kSampThreads + tid] = 0.f;
-      if (tid == 0) jstar = 0;
-      __syncthreads();
-      const float inv_w = 1.f / w, hi = lo + w * kSampThreads;
-#pragma unroll
-      for (int k = 0; k < R; ++k)
-        if (v[k] >= lo && v[k] < hi)
-          atomicAdd(&hist8[min(kSampThreads - 1, (int)((v[k] - lo) * inv_w)) * 8 + (tid & 7)], __expf(v[k] - M));
-      __syncthreads();
-      float h = 0.f;
-#pragma unroll
-      for (int c = 0; c < 8; ++c) h += hist8[tid * 8 + c];
-      hist[tid] = h;
-      __syncthreads();
-      for (int off = 1; off < kSampThreads; off <<= 1) {
-        const float x = tid + off < kSampThreads ? hist[tid + off] : 0.f;
-        __syncthreads();
-        hist[tid] += x;
-        __syncthreads();
-      }
-      if (hist[tid] + above >= target) atomicMax(&jstar, tid);
-      __syncthreads();
-      const int j = jstar;
-      above += j + 1 < kSampThreads ? hist[j + 1] : 0.f;
-      lo += j * w;
-      w *= 1.f / kSampThreads;
-      __syncthreads();
-    }
-  } else {
-    lo = -INFINITY;
-  }
-  const float cut = lo;
-  const float it = 1.f / fmaxf(temp, 1e-6f);
-  float part = 0.f;
-#pragma unroll
-  for (int k = 0; k < R; ++k)
-    if (v[k] >= cut) part += __expf((v[k] - M) * it);
-  scan[tid] = part;
-  if (tid == 0) pick = 0x7fffffff;
-  __syncthreads();
-  for (int off = 1; off < kSampThreads; off <<= 1) {
-    const float x = tid >= off ? scan[tid - off] : 0.f;
-    __syncthreads();
-    scan[tid] += x;
-    __syncthreads();
-  }
-  const float total = scan[kSampThreads - 1];
-  const float u = (float)(uniform01(seed, (uint64_t)st[ST_STEP]) * total);
-  const float before = tid ? scan[tid - 1] : 0.f;
-  if (u >= before && u < scan[tid] && part > 0.f) {
-    float run = before;
-    int sel = -1;
-#pragma unroll
-    for (int k = 0; k < R; ++k) {
-      if (sel < 0 && v[k] >= cut) {
-        run += __expf((v[k] - M) * it);
-        if (u < run) sel = tid + k * kSampThreads;
-      }
-    }
-    if (sel < 0)  // rounding at the thread's upper edge: its last kept token
-#pragma unroll
-      for (int k = 0; k < R; ++k)
-        if (v[k] >= cut) sel = tid + k * kSampThreads;
-    atomicMin(&pick, sel);
-  }
-  __syncthreads();
-  if (pick == 0x7fffffff) {  // u landed on a rounding gap at the very top: the most probable token
-#pragma unroll
-    for (int k = 0; k < R; ++k)
-      if (v[k] == M) atomicMin(&pick, tid + k * kSampThreads);
-    __syncthreads();
-  }
-  if (tid == 0) {
-    const int t = pick;
-    st[ST_TOK] = t;
-    st[ST_POS] += inc_pos;
-    st[ST_STEP] += 1;
-    if (host_tok) __hip_atomic_store(host_tok, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
+#include "decoder_body_sample_reg.hpp"
 }
 
 // ------------------------------------------------------------------ multi-block sampler --
@@ -1071,221 +581,34 @@ __global__ __launch_bounds__(kSampThreads) void k_sample_reg(const float* __rest
 // V 128256).  The workspace (floats, caller-owned so the chain can be graph-captured) is laid out in
 // decoder_common.hpp.
 
-// A: block max and its first index
+// A .. G of the chain: decoder_body_sb_*.hpp
 __global__ __launch_bounds__(kSbThreads) void k_sb_max(const float* __restrict__ logits, int V,
                                                        const uint8_t* __restrict__ mask, float* __restrict__ ws) {
-  const int chunk = (V + kSbBlocks - 1) / kSbBlocks, b0 = blockIdx.x * chunk, b1 = min(V, b0 + chunk);
-  float m = -INFINITY;
-  int mi = 0x7fffffff;
-#pragma unroll 8
-  for (int i = b0 + (int)threadIdx.x; i < b1; i += kSbThreads) {
-    const float l = sb_logit(logits, mask, i);
-    if (l > m) { m = l; mi = i; }
-  }
-  const float M = sb_reduce<kSbThreads>(m, true);
-  __shared__ int first;
-  if (threadIdx.x == 0) first = 0x7fffffff;
-  __syncthreads();
-  if (m == M) atomicMin(&first, mi);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    ws[SB_BMAX + blockIdx.x] = M;
-    ws[SB_BIDX + blockIdx.x] = __int_as_float(first);
-  }
+#include "decoder_body_sb_max.hpp"
 }
 
-// B / D: block mass (level 0) and the mass histogram of [lo, lo + 1024 w) (replicated bins, as k_sample_reg)
 template <int LEVEL>
 __global__ __launch_bounds__(kSbThreads) void k_sb_hist(const float* __restrict__ logits, int V,
                                                         const uint8_t* __restrict__ mask, float* __restrict__ ws) {
-  __shared__ float h8[kSbBins * 8];
-  const int tid = threadIdx.x;
-  float M, lo, w;
-  if (LEVEL == 0) {
-    float m = -INFINITY;
-    for (int b = 0; b < kSbBlocks; ++b) m = fmaxf(m, ws[SB_BMAX + b]);
-    M = m;
-    lo = M - 40.f;
-    w = 40.f / kSbBins * (1.f + 1e-6f);
-  } else {
-    M = ws[SB_SCAL + 0];
-    lo = ws[SB_SCAL + 2];
-    w = ws[SB_SCAL + 3];
-  }
-  for (int i = tid; i < kSbBins * 8; i += kSbThreads) h8[i] = 0.f;
-  __syncthreads();
-  const float inv_w = 1.f / w, hi = lo + w * kSbBins;
-  const int chunk = (V + kSbBlocks - 1) / kSbBlocks, b0 = blockIdx.x * chunk, b1 = min(V, b0 + chunk);
-  float z = 0.f;
-#pragma unroll 8
-  for (int i = b0 + tid; i < b1; i += kSbThreads) {
-    const float l = sb_logit(logits, mask, i);
-    const float e = __expf(l - M);
-    if (LEVEL == 0) z += e;
-    if (l >= lo && l < hi) atomicAdd(&h8[min(kSbBins - 1, (int)((l - lo) * inv_w)) * 8 + (tid & 7)], e);
-  }
-  if (LEVEL == 0) {
-    z = sb_reduce<kSbThreads>(z, false);
-    if (tid == 0) ws[SB_BZ + blockIdx.x] = z;
-  }
-  __syncthreads();
-  float* out = ws + SB_HIST + (long)blockIdx.x * kSbBins;
-  for (int t = tid; t < kSbBins; t += kSbThreads) {
-    float v = 0.f;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) v += h8[t * 8 + c];
-    out[t] = v;
-  }
+#include "decoder_body_sb_hist.hpp"
 }
 
-// C / E: one workgroup of 1024 threads sums the block histograms, finds the bin where the suffix
-// mass crosses top_p Z and narrows [lo, lo + 1024 w) to it (level 1: the cut)
 template <int LEVEL>
 __global__ __launch_bounds__(kSbBins) void k_sb_select(float top_p, float* __restrict__ ws) {
-  __shared__ float hs[kSbBins];
-  __shared__ int jstar;
-  const int tid = threadIdx.x;
-  float M, Z, lo, w, above;
-  if (LEVEL == 0) {
-    float m = -INFINITY;
-    for (int b = 0; b < kSbBlocks; ++b) m = fmaxf(m, ws[SB_BMAX + b]);
-    M = m;
-    Z = 0.f;
-    for (int b = 0; b < kSbBlocks; ++b) Z += ws[SB_BZ + b];
-    lo = M - 40.f;
-    w = 40.f / kSbBins * (1.f + 1e-6f);
-    above = 0.f;
-  } else {
-    M = ws[SB_SCAL + 0]; Z = ws[SB_SCAL + 1]; lo = ws[SB_SCAL + 2]; w = ws[SB_SCAL + 3]; above = ws[SB_SCAL + 4];
-  }
-  float h = 0.f;
-  for (int b = 0; b < kSbBlocks; ++b) h += ws[SB_HIST + (long)b * kSbBins + tid];
-  hs[tid] = h;
-  if (tid == 0) jstar = 0;
-  __syncthreads();
-  for (int off = 1; off < kSbBins; off <<= 1) {  // suffix sums
-    const float x = tid + off < kSbBins ? hs[tid + off] : 0.f;
-    __syncthreads();
-    hs[tid] += x;
-    __syncthreads();
-  }
-  if (hs[tid] + above >= top_p * Z) atomicMax(&jstar, tid);
-  __syncthreads();
-  if (tid == 0) {
-    const int j = jstar;
-    ws[SB_SCAL + 0] = M;
-    ws[SB_SCAL + 1] = Z;
-    ws[SB_SCAL + 4] = above + (j + 1 < kSbBins ? hs[j + 1] : 0.f);
-    ws[SB_SCAL + 2] = lo + j * w;
-    ws[SB_SCAL + 3] = w * (1.f / kSbBins);
-    ws[SB_SCAL + 5] = lo + j * w;  // the cut after the last level
-  }
+#include "decoder_body_sb_select.hpp"
 }
 
-// F: kept (tempered) mass per block; with top_p >= 1 the cut is -inf and M comes from the maxima
 __global__ __launch_bounds__(kSbThreads) void k_sb_part(const float* __restrict__ logits, int V,
                                                         const uint8_t* __restrict__ mask, float temp, int nucleus,
                                                         float* __restrict__ ws) {
-  float M, cut;
-  if (nucleus) {
-    M = ws[SB_SCAL + 0];
-    cut = ws[SB_SCAL + 5];
-  } else {
-    float m = -INFINITY;
-    for (int b = 0; b < kSbBlocks; ++b) m = fmaxf(m, ws[SB_BMAX + b]);
-    M = m;
-    cut = -INFINITY;
-    if (blockIdx.x == 0 && threadIdx.x == 0) { ws[SB_SCAL + 0] = M; ws[SB_SCAL + 5] = cut; }
-  }
-  const float it = 1.f / fmaxf(temp, 1e-6f);
-  const int chunk = (V + kSbBlocks - 1) / kSbBlocks, b0 = blockIdx.x * chunk, b1 = min(V, b0 + chunk);
-  float part = 0.f;
-#pragma unroll 8
-  for (int i = b0 + (int)threadIdx.x; i < b1; i += kSbThreads) {
-    const float l = sb_logit(logits, mask, i);
-    if (l >= cut) part += __expf((l - M) * it);
-  }
-  part = sb_reduce<kSbThreads>(part, false);
-  if (threadIdx.x == 0) ws[SB_BPART + blockIdx.x] = part;
+#include "decoder_body_sb_part.hpp"
 }
 
-// G: the draw -- the block whose prefix range holds u, then inside its slice (thread t owns the
-// contiguous elements [t c, t c + c)) the token; state update as k_sample_reg
 __global__ __launch_bounds__(kSbBins) void k_sb_draw(const float* __restrict__ logits, int V,
                                                      const uint8_t* __restrict__ mask, float temp, uint64_t seed,
                                                      const float* __restrict__ ws, int32_t* __restrict__ st,
                                                      int inc_pos, int32_t* host_tok) {
-  __shared__ float scan[kSbBins];
-  __shared__ int pick;
-  __shared__ float base_u;
-  __shared__ int blk;
-  const int tid = threadIdx.x;
-  const float M = ws[SB_SCAL + 0], cut = ws[SB_SCAL + 5];
-  const float it = 1.f / fmaxf(temp, 1e-6f);
-  if (tid == 0) {
-    double total = 0.0;
-    for (int b = 0; b < kSbBlocks; ++b) total += ws[SB_BPART + b];
-    const double u = uniform01(seed, (uint64_t)st[ST_STEP]) * total;
-    double run = 0.0;
-    int bb = -1;
-    for (int b = 0; b < kSbBlocks; ++b) {
-      const double p = ws[SB_BPART + b];
-      if (p > 0.0) {
-        if (u < run + p) { bb = b; break; }
-        bb = b;  // rounding at the very end: the last block with mass
-      }
-      run += p;
-    }
-    if (bb >= 0 && u >= run + ws[SB_BPART + bb]) run -= ws[SB_BPART + bb];
-    blk = bb;
-    base_u = (float)(u - run);
-    pick = 0x7fffffff;
-  }
-  __syncthreads();
-  const int chunk = (V + kSbBlocks - 1) / kSbBlocks;
-  if (blk >= 0) {
-    const int b0 = blk * chunk, b1 = min(V, b0 + chunk);
-    const int per = (b1 - b0 + kSbBins - 1) / kSbBins;
-    const int t0 = b0 + tid * per, t1 = min(b1, t0 + per);
-    float part = 0.f;
-    for (int i = t0; i < t1; ++i) {
-      const float l = sb_logit(logits, mask, i);
-      if (l >= cut) part += __expf((l - M) * it);
-    }
-    scan[tid] = part;
-    __syncthreads();
-    for (int off = 1; off < kSbBins; off <<= 1) {
-      const float x = tid >= off ? scan[tid - off] : 0.f;
-      __syncthreads();
-      scan[tid] += x;
-      __syncthreads();
-    }
-    const float u = base_u, before = tid ? scan[tid - 1] : 0.f;
-    if (part > 0.f && u >= before && (u < scan[tid] || tid == kSbBins - 1 || scan[tid] >= scan[kSbBins - 1])) {
-      float run = before;
-      int sel = -1;
-      for (int i = t0; i < t1; ++i) {
-        const float l = sb_logit(logits, mask, i);
-        if (l < cut) continue;
-        sel = i;
-        run += __expf((l - M) * it);
-        if (u < run) break;
-      }
-      if (sel >= 0) atomicMin(&pick, sel);
-    }
-    __syncthreads();
-  }
-  if (tid == 0) {
-    int t = pick;
-    if (t == 0x7fffffff) {  // rounding gap: the most probable token (first block holding the max)
-      for (int b = 0; b < kSbBlocks; ++b)
-        if (ws[SB_BMAX + b] == M) { t = __float_as_int(ws[SB_BIDX + b]); break; }
-    }
-    st[ST_TOK] = t;
-    st[ST_POS] += inc_pos;
-    st[ST_STEP] += 1;
-    if (host_tok) __hip_atomic_store(host_tok, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
+#include "decoder_body_sb_draw.hpp"
 }
 
 // ------------------------------------------------------- prefill attention over the KV cache --
@@ -1530,31 +853,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
 }
 
 // ------------------------------------------------------------------ host dispatch --
-template <int V>
-using ic = std::integral_constant<int, V>;
-
-// the runtime shape as compile-time constants: f(ic<D>) for d = head dim / 64 in 1..4, and
-// f(ic<D>, ic<G>) with g = heads per workgroup in {1, 2, 4, 8}
-template <class F>
-void with_d(int d, F f) {
-  switch (d) {
-    case 1: f(ic<1>{}); break;
-    case 2: f(ic<2>{}); break;
-    case 3: f(ic<3>{}); break;
-    default: f(ic<4>{}); break;
-  }
-}
-template <class F>
-void with_d_g(int d, int g, F f) {
-  with_d(d, [&](auto D) {
-    switch (g) {
-      case 2: f(D, ic<2>{}); break;
-      case 4: f(D, ic<4>{}); break;
-      case 8: f(D, ic<8>{}); break;
-      default: f(D, ic<1>{}); break;
-    }
-  });
-}
+// ic, with_d, with_d_g: decoder_common.hpp
 
 // f(ic<MODE>, bool_constant<RMS>) for a GEMV epilogue mode (0, 1, 2, 4); false: no such mode
 template <class F>

@@ -330,14 +330,19 @@ class CausalLM:
         return cls(cfg, tensors, device, quant=quant if device != "cpu" else "bf16", ggml_types=types), tok
 
     # ------------------------------------------------------------- pieces --
+    def _dense(self, w):
+        """The bf16 matrix the MFMA GEMM reads: a 4- / 8-bit one is dequantised into the shared scratch."""
+        if not isinstance(w, Q4Weight):
+            return w
+        n_el = w.shape[0] * w.shape[1]
+        if self._q4_scratch is None or self._q4_scratch.numel() < n_el:
+            self._q4_scratch = torch.empty(n_el, dtype=torch.bfloat16, device=self.device)
+        return w.dequant(self.L, self._q4_scratch[:n_el].view(w.shape))
+
     def _mm(self, mode: int, x: torch.Tensor, w, out_cols: int, res: Optional[torch.Tensor] = None):
         """x [M, K] @ w[N, K]^T with a fused epilogue; HIP MFMA on the GPU, torch on the CPU."""
         M, K = x.shape
-        if isinstance(w, Q4Weight):  # prefill: dequantise into the shared bf16 scratch
-            n_el = w.shape[0] * w.shape[1]
-            if self._q4_scratch is None or self._q4_scratch.numel() < n_el:
-                self._q4_scratch = torch.empty(n_el, dtype=torch.bfloat16, device=self.device)
-            w = w.dequant(self.L, self._q4_scratch[:n_el].view(w.shape))
+        w = self._dense(w)  # prefill runs on bf16 weights
         if not self.hip:
             if mode == 2:
                 up, gate = self._split_ug(x @ w.T)
@@ -456,6 +461,29 @@ class CausalLM:
         return logits[0, : cfg.vocab].float()
 
 
+def _run_step(eng, span: int):
+    """One decode step of a DecodeEngine or a BatchDecodeEngine for the attention span ``span``: eager
+    launches, or the replay of the step captured for that span (captured on its first use)."""
+    if not eng.use_graph:
+        eng._enqueue_step(span)
+        return
+    g = eng.graphs.get(span)
+    if g is None:
+        # warm up once outside capture (first-launch code-object loading), then capture
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        saved = eng.st.clone()
+        with torch.cuda.stream(side):
+            eng._enqueue_step(span)
+        torch.cuda.current_stream().wait_stream(side)
+        eng.st.copy_(saved)  # the warm-up step is undone: same state, cache rows rewritten next
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            eng._enqueue_step(span)
+        eng.graphs[span] = g
+    g.replay()
+
+
 class DecodeEngine:
     """Token generation with no host compute in the loop (K18): prompt prefill on the MFMA GEMMs
     and the causal MFMA attention, then per token ONE replay of a HIP graph holding the whole
@@ -538,24 +566,7 @@ class DecodeEngine:
         # the split-L one sized for the cache capacity (a split grid costs ~9 us more per layer on
         # short caches: profiles/r2_decode_splits_gqa.jsonl); the host knows the position
         span = self.m.cfg.n_ctx if self.m.pos + 1 > 512 else min(512, self.m.cfg.n_ctx)
-        if not self.use_graph:
-            self._enqueue_step(span)
-            return
-        g = self.graphs.get(span)
-        if g is None:
-            # warm up once outside capture (first-launch code-object loading), then capture
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            saved = self.st.clone()
-            with torch.cuda.stream(side):
-                self._enqueue_step(span)
-            torch.cuda.current_stream().wait_stream(side)
-            self.st.copy_(saved)  # the warm-up step is undone: same state, cache row rewritten next
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._enqueue_step(span)
-            self.graphs[span] = g
-        g.replay()
+        _run_step(self, span)
 
     def first_token(self, ids: List[int]) -> int:
         """Prefill the prompt (KV cache rows 0..n-1) and sample the first token on the device."""
@@ -675,25 +686,35 @@ class BatchDecodeEngine:
         self.st[slot].copy_(self._rec, non_blocking=True)
         torch.cuda.current_stream().synchronize()  # _rec is reused by the next write
 
-    def admit(self, ids: List[int], seed: Optional[int] = None):
-        """Prefill ``ids`` into a free slot and sample its first token: (slot, first_token)."""
-        m = self.m
+    def _free_slot(self, ids: List[int]) -> int:
+        """The lowest slot that is neither live nor pending, for a prompt that fits the context."""
         free = [b for b, p in enumerate(self.pos) if p is None and b not in self.pend]
         if not free:
             raise RuntimeError(f"all {self.S} sequence slots are in use")
-        if not ids or len(ids) >= m.cfg.n_ctx:
-            raise ValueError(f"a prompt of {len(ids)} tokens leaves no room in a context of {m.cfg.n_ctx}")
-        slot = free[0]
+        if not ids or len(ids) >= self.m.cfg.n_ctx:
+            raise ValueError(f"a prompt of {len(ids)} tokens leaves no room in a context of {self.m.cfg.n_ctx}")
+        return free[0]
+
+    def _seed(self, seed: Optional[int]) -> int:
+        return self.seed if seed is None else int(seed) & 0xFFFFFFFFFFFFFFFF
+
+    def _first_token(self, slot: int, n: int, sd: int, logits: torch.Tensor):
+        """A prefilled prompt of n tokens goes live: its record, its logits row, its first draw (enqueued)."""
+        self._write_state(slot, [n, 0, 0, 1, sd & 0xFFFFFFFF, sd >> 32, 0, 0])
+        self.logits[slot, : self.m.cfg.vocab].copy_(logits)
+        self._sample(slot, 1, inc_pos=0)
+
+    def admit(self, ids: List[int], seed: Optional[int] = None):
+        """Prefill ``ids`` into a free slot and sample its first token: (slot, first_token)."""
+        m = self.m
+        slot = self._free_slot(ids)
         saved = (m.kv, m.pos)
         m.kv, m.pos = self.kv[slot], 0  # the eager forward appends to whatever cache the model points at
         try:
             logits = m.forward(ids)
         finally:
             m.kv, m.pos = saved
-        sd = self.seed if seed is None else int(seed) & 0xFFFFFFFFFFFFFFFF
-        self._write_state(slot, [len(ids), 0, 0, 1, sd & 0xFFFFFFFF, sd >> 32, 0, 0])
-        self.logits[slot, : m.cfg.vocab].copy_(logits)
-        self._sample(slot, 1, inc_pos=0)
+        self._first_token(slot, len(ids), self._seed(seed), logits)
         torch.cuda.current_stream().synchronize()
         self.pos[slot] = len(ids)
         return slot, int(self.host_tok[slot])
@@ -727,17 +748,12 @@ class BatchDecodeEngine:
         m = self.m
         if not m.prefill_kernel:
             raise ValueError(f"head dim {m.cfg.head_dim}: the batched prefill needs 64 or 128 (use admit)")
-        free = [b for b, p in enumerate(self.pos) if p is None and b not in self.pend]
-        if not free:
-            raise RuntimeError(f"all {self.S} sequence slots are in use")
-        if not ids or len(ids) >= m.cfg.n_ctx:
-            raise ValueError(f"a prompt of {len(ids)} tokens leaves no room in a context of {m.cfg.n_ctx}")
-        sd = self.seed if seed is None else int(seed) & 0xFFFFFFFFFFFFFFFF
+        slot = self._free_slot(ids)
         ids = list(ids)
         R = len(self._pfx_ids or ())
         # carrying is all or nothing: the whole kept prefix, and at least one token of the request's own
-        self.pend[free[0]] = [ids, 0, sd, R > 0 and len(ids) > R and ids[:R] == self._pfx_ids]
-        return free[0]
+        self.pend[slot] = [ids, 0, self._seed(seed), R > 0 and len(ids) > R and ids[:R] == self._pfx_ids]
+        return slot
 
     def set_prefix(self, ids: Optional[List[int]], chunk: int) -> int:
         """Name the prompt prefix that requests share and return R = (len(ids) // chunk) * chunk, the tokens
@@ -800,24 +816,29 @@ class BatchDecodeEngine:
         self._pf = w
         return w
 
-    def _dense(self, w):
-        """The bf16 matrix the MFMA GEMM reads: a 4- / 8-bit one is dequantised into the model's scratch."""
-        if not isinstance(w, Q4Weight):
-            return w
-        m = self.m
-        n_el = w.shape[0] * w.shape[1]
-        if m._q4_scratch is None or m._q4_scratch.numel() < n_el:
-            m._q4_scratch = torch.empty(n_el, dtype=torch.bfloat16, device=m.device)
-        return w.dequant(m.L, m._q4_scratch[:n_el].view(w.shape))
-
     def _pf_mm(self, mode, x, M, w, res, out, what):
         """out[:M] = epilogue(x[:M] @ w^T) on nomic_gemm; x / res / out are workspace row blocks."""
         from .nomic import _chk, _stream
-        wd = self._dense(w)
+        wd = self.m._dense(w)
         N, K = wd.shape
         rp, ldr = (res.data_ptr(), res.stride(0)) if res is not None else (None, 0)
         _chk(self.m.L.nomic_gemm(mode, x.data_ptr(), x.stride(0), wd.data_ptr(), K, M, N, K, out.data_ptr(),
                                  out.stride(0), rp, ldr, None, None, 0, _stream()), what)
+
+    def _prefix_plan(self):
+        """What the shared prefix asks of the next pass, from host state alone: (hits, donor, held).  Once the
+        rows are captured, a carrying request still at offset 0 starts from copied rows (a hit).  Until then one
+        carrying request (the donor) computes them and the others wait at offset 0 (held).  The donor stays the
+        donor while it is pending (a request submitted into a lower slot meanwhile is held like the rest); after
+        its release the lowest carrying slot takes over, from its own offset 0."""
+        carrying = [b for b in sorted(self.pend) if self.pend[b][3]] if self._pfx_ids else []
+        if self._pfx_ready:
+            return [b for b in carrying if self.pend[b][1] == 0], None, []
+        if not carrying:
+            return [], None, []
+        if self._pfx_donor not in carrying:
+            self._pfx_donor = carrying[0]
+        return [], self._pfx_donor, [b for b in carrying if b != self._pfx_donor]
 
     @torch.no_grad()
     def prefill(self, chunk: int) -> Dict[int, int]:
@@ -837,25 +858,14 @@ class BatchDecodeEngine:
         m, cfg, L, S = self.m, self.m.cfg, self.m.L, self.S
         H, KVH, hd = cfg.heads, cfg.kv_heads, cfg.head_dim
         w = self._prefill_ws(chunk)
-        # the shared prefix: once captured, a carrying request still at offset 0 starts from copied rows (a hit);
-        # until then one carrying request (the donor) computes them and the others wait at offset 0 (held)
-        carrying = [b for b in sorted(self.pend) if self.pend[b][3]] if R else []
-        donor, held = None, ()
-        if self._pfx_ready:
-            hits = [b for b in carrying if self.pend[b][1] == 0]
-            if hits:  # one launch for every such slot of the pass, ahead of its first kernel
-                self._fanout(self._pfx_buf, R, self.kv, cfg.n_ctx, self.kv.stride(0), hits, S, R)
-                for b in hits:
-                    self.pend[b][1] = R
-                self.prefix_hits += len(hits)
-                self.prefix_rows_reused += R * len(hits)
-        elif carrying:
-            # the donor stays the donor while it is pending (a request submitted into a lower slot meanwhile is
-            # held like the rest); after its release the lowest carrying slot takes over, from its own offset 0
-            if self._pfx_donor not in carrying:
-                self._pfx_donor = carrying[0]
-            donor = self._pfx_donor
-            held = [b for b in carrying if b != donor]
+        hits, donor, held = self._prefix_plan()
+        if hits:  # one launch for every such slot of the pass, ahead of its first kernel
+            self._fanout(self._pfx_buf, R, self.kv, cfg.n_ctx, self.kv.stride(0), hits, S, R)
+            for b in hits:
+                self.pend[b][1] = R
+            self.prefix_hits += len(hits)
+            self.prefix_rows_reused += R * len(hits)
+        # pack: the next chunk of every pending slot that is not held, as one token matrix
         segs, toks, ends = [], [], []
         for slot in sorted(self.pend):
             if slot in held:
@@ -908,6 +918,7 @@ class BatchDecodeEngine:
                 self._pf_mm(4, w["hl"], k, m.head, None, w["lg"], "gemm head")
         finally:
             L.nomic_gemm_set_variant(prev)
+        # finish: offsets, the donor's rows, and the prompts that ended go live
         for _, n, _, slot in segs:
             self.pend[slot][1] += n
         if donor is not None and self.pend[donor][1] >= R:
@@ -918,9 +929,7 @@ class BatchDecodeEngine:
         out = {}
         for i, (slot, _) in enumerate(ends):
             ids, _, sd = self.pend[slot][:3]
-            self._write_state(slot, [len(ids), 0, 0, 1, sd & 0xFFFFFFFF, sd >> 32, 0, 0])
-            self.logits[slot, : cfg.vocab].copy_(w["lg"][i, : cfg.vocab])
-            self._sample(slot, 1, inc_pos=0)
+            self._first_token(slot, len(ids), sd, w["lg"][i, : cfg.vocab])
         torch.cuda.current_stream().synchronize()
         for slot, _ in ends:
             self.pos[slot] = len(self.pend.pop(slot)[0])
@@ -991,24 +1000,7 @@ class BatchDecodeEngine:
             if self.pos[b] >= n_ctx:
                 raise ValueError(f"slot {b}: context window of {n_ctx} tokens exceeded")
         span = n_ctx if max(self.pos[b] for b in live) + 1 > 512 else min(512, n_ctx)
-        if not self.use_graph:
-            self._enqueue_step(span)
-        else:
-            g = self.graphs.get(span)
-            if g is None:
-                # warm up once outside capture (first-launch code-object loading), then capture
-                side = torch.cuda.Stream()
-                side.wait_stream(torch.cuda.current_stream())
-                saved = self.st.clone()
-                with torch.cuda.stream(side):
-                    self._enqueue_step(span)
-                torch.cuda.current_stream().wait_stream(side)
-                self.st.copy_(saved)  # the warm-up step is undone: same state, cache rows rewritten next
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    self._enqueue_step(span)
-                self.graphs[span] = g
-            g.replay()
+        _run_step(self, span)
         torch.cuda.current_stream().synchronize()
         self.steps += 1
         out = {}
