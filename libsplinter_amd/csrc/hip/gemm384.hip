@@ -15,14 +15,30 @@
 // so a lane's accumulator holds four CONSECUTIVE output columns of one row: k_gemm_rln's per-wave
 // layout and fragment read order.
 //
-// K loop: k_gemm_rln's (gemm_rln.hip).  A second copy: with the loop in a shared template hipcc
-// spilled 35-40 registers in k_gemm_rln (profiles/gemm384/README.md).  BK = 32, LDS rings of
-// three W stages (384 x 32 bf16, 24 KB) and two A stages (256 x 32, 16 KB), 104 KB; 2 A + 3 W LDS-DMA
-// wave-instructions per wave per stage, issued two ahead of each MFMA pair; counted vmcnt + one raw
-// s_barrier per stage; 64-B rows with the 16-B chunk c of row r stored at c ^ ((r >> 1) & 3), applied
-// to the global source address and to the read address.  Ring discipline: a staged slot is read only
-// after the issuing wave's counted wait and a barrier the reader has passed; a slot is restaged only
-// after a barrier that follows its last read.
+// K loop, 32-wide stages (BK = 32; K % 64 != 0, or NOMIC_GEMM384_BK=32): k_gemm_rln's (gemm_rln.hip).  A
+// second copy: with the loop in a shared template hipcc spilled 35-40 registers in k_gemm_rln
+// (profiles/gemm384/README.md).  LDS rings of three W stages (384 x 32 bf16, 24 KB) and two A stages
+// (256 x 32, 16 KB), 104 KB; 2 A + 3 W LDS-DMA wave-instructions per wave per stage, issued two ahead of
+// each MFMA pair; counted vmcnt + one raw s_barrier per stage; 64-B rows with the 16-B chunk c of row r
+// stored at c ^ ((r >> 1) & 3), applied to the global source address and to the read address.  Ring
+// discipline: a staged slot is read only after the issuing wave's counted wait and a barrier the reader
+// has passed; a slot is restaged only after a barrier that follows its last read.
+//
+// K loop, 64-wide stages (BK = 64, the default where K % 64 == 0): two slots of [W 384 rows x 128 B |
+// A 256 rows x 128 B], 2 x 80 KB = 160 KB, so one s_waitcnt and one s_barrier per TWO MFMA K-steps (12
+// per tile at K = 768 instead of 24) and whole 128-B lines per DMA row piece.  A DMA wave-instruction
+// covers 8 rows x 128 B (lane -> row lane >> 3, chunk lane & 7), 4 A + 6 W per wave per stage, LDS
+// destination lane-linear 1 KB; chunk c of row r is stored at c ^ ((r >> 1) & 7) (16 distinct bank quads
+// in each ds_read_b128 lane group for both K-steps; & 3 gives 8).  A stage is two passes of the 32-wide
+// loop's six-pair body, K-step 2T then 2T + 1, so every accumulator sees ascending k in steps of 32
+// and the output has the bits of the 32-wide loop.  Ring discipline: iteration T waits vmcnt(0)
+// (everything in flight is stage T, issued during iteration T - 1), then one raw barrier; stage T + 1's
+// ten pieces then enter the other slot, whose last readers all passed this barrier, two ahead of each
+// of the first five MFMA pairs; no barrier follows the last stage.
+// Measured (profiles/gemm384_bk64/README.md), 32768 tokens, forms interleaved in one process:
+// SwiGLU 268.9 -> 247.9 us, qkv + RoPE 124.6 -> 116.3 us; mixed step 11.22-11.31 -> 10.92-10.97 ms.
+// Measured and removed: one piece ahead of each of the first ten pairs: equal on the SwiGLU shape
+// (254.1 against 252.9 us), slower on the qkv shape (118.9 against 115.0 us).
 //
 // Epilogues run from registers, no LDS image.  pack_upgate and pack_qkv place up / gate and the NEOX
 // pair (d, d + 32) in n-tiles 2p and 2p + 1 at the same in-tile column, so SwiGLU and RoPE are
@@ -116,7 +132,16 @@ constexpr int kNW = 3, kNA = 2;
 constexpr int kLdsBytes = kNW * kWBytes + kNA * kABytes;  // 104 KB: [W ring | A ring]
 static_assert(kLdsBytes <= 160 * 1024, "LDS budget");
 
-template <int MODE>
+// 64-wide stages (BK = 64): two slots of [W | A] with 128-B rows, the 16-B chunk c of row r stored at
+// c ^ ((r >> 1) & 7) (k_attn3's K image: 16 distinct bank quads in every ds_read_b128 lane group, for
+// both K-steps of a stage; (r >> 1) & 3 on 128-B rows does not give that).
+constexpr int kWBytes2 = kBN * 128, kABytes2 = kBM * 128;  // 48 KB + 32 KB
+constexpr int kSlotBytes = kWBytes2 + kABytes2;
+constexpr int kLdsBytes2 = 2 * kSlotBytes;                 // 160 KB
+static_assert(kLdsBytes2 <= 160 * 1024, "LDS budget");
+__device__ __forceinline__ int swz128(int r, int c) { return c ^ ((r >> 1) & 7); }
+
+template <int MODE, int BK>
 __global__ __launch_bounds__(kThreads, 1) void k_gemm384(const uint16_t* __restrict__ A, long lda,
                                                          const uint16_t* __restrict__ W, long ldw, int K,
                                                          int mtiles, int ntiles, Epi384 ep) {
@@ -128,6 +153,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_gemm384(const uint16_t* __restr
   constexpr int GA = kBM / 16 / kWaves, GW = kBN / 16 / kWaves;  // LDS-DMA wave-instructions per wave per stage
   static_assert(GA == 2 && GW == 3 && MT == 4, "wait_vm's cases and the epilogues assume this split");
   static_assert(MODE == NOMIC_EPI_STORE || MODE == NOMIC_EPI_SWIGLU || MODE == NOMIC_EPI_ROPE, "epilogues");
+  static_assert(BK == 32 || BK == 64, "K per stage");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 1, wn = wave & 1;
@@ -137,92 +163,170 @@ __global__ __launch_bounds__(kThreads, 1) void k_gemm384(const uint16_t* __restr
   A += m0 * lda;
   W += n0 * ldw;
 
-  // ---- per-lane LDS-DMA sources: a wave-instruction covers 16 rows x 64 B, lane -> (row, chunk)
-  const int drow = lane >> 2, dpc = lane & 3;
-  uint32_t offA[GA];
-#pragma unroll
-  for (int i = 0; i < GA; ++i) {
-    const int r = (wave + kWaves * i) * 16 + drow;
-    const long gr = (m0 + r < ep.M) ? r : ep.M - 1 - m0;  // tail rows re-read row M-1, never stored
-    offA[i] = (uint32_t)(gr * lda + swz(r, dpc) * 8);
-  }
-  uint32_t offW[GW];
-#pragma unroll
-  for (int i = 0; i < GW; ++i) {
-    const int r = (wave + kWaves * i) * 16 + drow;
-    offW[i] = (uint32_t)(r * ldw + swz(r, dpc) * 8);
-  }
-  const int nk = K / kBK;
-  // ring slot of stage t: t % kNW (W), t % kNA (A) -- stages enter each ring in order
-  auto glds_w = [&](int t, int i) {
-    __builtin_amdgcn_global_load_lds((gbl_void*)(W + (long)t * kBK + offW[i]),
-                                     (lds_void*)(smem + (t % kNW) * kWBytes + (wave + kWaves * i) * 1024), 16, 0, 0);
-  };
-  auto glds_a = [&](int t, int i) {
-    __builtin_amdgcn_global_load_lds((gbl_void*)(A + (long)t * kBK + offA[i]),
-                                     (lds_void*)(smem + kABase + (t % kNA) * kABytes + (wave + kWaves * i) * 1024),
-                                     16, 0, 0);
-  };
-  // op u (0 .. GA+GW-1) of the loads iteration s issues: stage A(s + LA), then W(s + LW) (the
-  // counted wait at the top of an iteration relies on that order)
-  constexpr int kOps = GA + GW;
-  static_assert(kOps <= kNT, "two DMAs ahead of each of the kNT / 2 MFMA pairs cover a stage's loads");
-  auto issue_op = [&](int s, int u) {
-    const int tw = s + LW, ta = s + LA;
-    if (u < GA) { if (ta >= 0 && ta < nk) glds_a(ta, u); }
-    else if (tw >= 0 && tw < nk) glds_w(tw, u - GA);
-  };
-  auto issue = [&](int s) {
-#pragma unroll
-    for (int u = 0; u < kOps; ++u) issue_op(s, u);
-  };
-  // W(t + LW - 1) was issued after A(t): it may stay in flight at the top of iteration t
-  auto younger = [&](int t) -> int { return t + LW - 1 < nk ? GW : 0; };
-
-  // fragment read: row = base16 + (lane & 15), logical chunk lane >> 4
-  const int fl = (lane & 15) * kRowBytes + (swz(lane & 15, lane >> 4) << 4);
-  const int aoff = kABase + (wr * RW) * kRowBytes + fl;
-  const int woff = (wn * kWN) * kRowBytes + fl;
-
   f32x4 acc[MT][kNT];
 #pragma unroll
   for (int i = 0; i < MT; ++i)
 #pragma unroll
     for (int j = 0; j < kNT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  for (int s = -LW; s < 0; ++s) issue(s);
-  for (int t = 0; t < nk; ++t) {
-    wait_vm(younger(t));
-    raw_barrier();  // stage t visible to every wave; every wave is done with stage t-1's slots
-    const char* bw = smem + (t % kNW) * kWBytes;
-    const char* ba = smem + (t % kNA) * kABytes;
-    // A fragments for the whole stage, W fragments two n-tiles at a time with the next pair's reads
-    // issued ahead of the current pair's MFMAs (sched_barrier pins the pairs); the stage's five DMAs
-    // go two ahead of each of the first MFMA pairs, in issue order.
-    bf16x8 af[MT], w0, w1, x0, x1;
+  if constexpr (BK == 32) {
+    // ---- per-lane LDS-DMA sources: a wave-instruction covers 16 rows x 64 B, lane -> (row, chunk)
+    const int drow = lane >> 2, dpc = lane & 3;
+    uint32_t offA[GA];
 #pragma unroll
-    for (int i = 0; i < MT; ++i) af[i] = *(const bf16x8*)(ba + aoff + i * 16 * kRowBytes);
-    w0 = *(const bf16x8*)(bw + woff);
-    w1 = *(const bf16x8*)(bw + woff + 16 * kRowBytes);
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int jp = 0; jp < kNT / 2; ++jp) {
-#pragma unroll
-      for (int u = 2 * jp; u < 2 * jp + 2; ++u)
-        if (u < kOps) issue_op(t, u);
-      if (jp + 1 < kNT / 2) {
-        x0 = *(const bf16x8*)(bw + woff + (2 * (jp + 1)) * 16 * kRowBytes);
-        x1 = *(const bf16x8*)(bw + woff + (2 * (jp + 1) + 1) * 16 * kRowBytes);
-      }
-#pragma unroll
-      for (int i = 0; i < MT; ++i) {
-        acc[i][2 * jp] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0, af[i], acc[i][2 * jp], 0, 0, 0);
-        acc[i][2 * jp + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1, af[i], acc[i][2 * jp + 1], 0, 0, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      w0 = x0;
-      w1 = x1;
+    for (int i = 0; i < GA; ++i) {
+      const int r = (wave + kWaves * i) * 16 + drow;
+      const long gr = (m0 + r < ep.M) ? r : ep.M - 1 - m0;  // tail rows re-read row M-1, never stored
+      offA[i] = (uint32_t)(gr * lda + swz(r, dpc) * 8);
     }
-    __builtin_amdgcn_s_setprio(0);
+    uint32_t offW[GW];
+#pragma unroll
+    for (int i = 0; i < GW; ++i) {
+      const int r = (wave + kWaves * i) * 16 + drow;
+      offW[i] = (uint32_t)(r * ldw + swz(r, dpc) * 8);
+    }
+    const int nk = K / kBK;
+    // ring slot of stage t: t % kNW (W), t % kNA (A) -- stages enter each ring in order
+    auto glds_w = [&](int t, int i) {
+      __builtin_amdgcn_global_load_lds((gbl_void*)(W + (long)t * kBK + offW[i]),
+                                       (lds_void*)(smem + (t % kNW) * kWBytes + (wave + kWaves * i) * 1024), 16, 0, 0);
+    };
+    auto glds_a = [&](int t, int i) {
+      __builtin_amdgcn_global_load_lds((gbl_void*)(A + (long)t * kBK + offA[i]),
+                                       (lds_void*)(smem + kABase + (t % kNA) * kABytes + (wave + kWaves * i) * 1024),
+                                       16, 0, 0);
+    };
+    // op u (0 .. GA+GW-1) of the loads iteration s issues: stage A(s + LA), then W(s + LW) (the
+    // counted wait at the top of an iteration relies on that order)
+    constexpr int kOps = GA + GW;
+    static_assert(kOps <= kNT, "two DMAs ahead of each of the kNT / 2 MFMA pairs cover a stage's loads");
+    auto issue_op = [&](int s, int u) {
+      const int tw = s + LW, ta = s + LA;
+      if (u < GA) { if (ta >= 0 && ta < nk) glds_a(ta, u); }
+      else if (tw >= 0 && tw < nk) glds_w(tw, u - GA);
+    };
+    auto issue = [&](int s) {
+#pragma unroll
+      for (int u = 0; u < kOps; ++u) issue_op(s, u);
+    };
+    // W(t + LW - 1) was issued after A(t): it may stay in flight at the top of iteration t
+    auto younger = [&](int t) -> int { return t + LW - 1 < nk ? GW : 0; };
+
+    // fragment read: row = base16 + (lane & 15), logical chunk lane >> 4
+    const int fl = (lane & 15) * kRowBytes + (swz(lane & 15, lane >> 4) << 4);
+    const int aoff = kABase + (wr * RW) * kRowBytes + fl;
+    const int woff = (wn * kWN) * kRowBytes + fl;
+
+    for (int s = -LW; s < 0; ++s) issue(s);
+    for (int t = 0; t < nk; ++t) {
+      wait_vm(younger(t));
+      raw_barrier();  // stage t visible to every wave; every wave is done with stage t-1's slots
+      const char* bw = smem + (t % kNW) * kWBytes;
+      const char* ba = smem + (t % kNA) * kABytes;
+      // A fragments for the whole stage, W fragments two n-tiles at a time with the next pair's reads
+      // issued ahead of the current pair's MFMAs (sched_barrier pins the pairs); the stage's five DMAs
+      // go two ahead of each of the first MFMA pairs, in issue order.
+      bf16x8 af[MT], w0, w1, x0, x1;
+#pragma unroll
+      for (int i = 0; i < MT; ++i) af[i] = *(const bf16x8*)(ba + aoff + i * 16 * kRowBytes);
+      w0 = *(const bf16x8*)(bw + woff);
+      w1 = *(const bf16x8*)(bw + woff + 16 * kRowBytes);
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int jp = 0; jp < kNT / 2; ++jp) {
+#pragma unroll
+        for (int u = 2 * jp; u < 2 * jp + 2; ++u)
+          if (u < kOps) issue_op(t, u);
+        if (jp + 1 < kNT / 2) {
+          x0 = *(const bf16x8*)(bw + woff + (2 * (jp + 1)) * 16 * kRowBytes);
+          x1 = *(const bf16x8*)(bw + woff + (2 * (jp + 1) + 1) * 16 * kRowBytes);
+        }
+#pragma unroll
+        for (int i = 0; i < MT; ++i) {
+          acc[i][2 * jp] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0, af[i], acc[i][2 * jp], 0, 0, 0);
+          acc[i][2 * jp + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1, af[i], acc[i][2 * jp + 1], 0, 0, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        w0 = x0;
+        w1 = x1;
+      }
+      __builtin_amdgcn_s_setprio(0);
+    }
+  } else {
+    // ---- 64-wide stages: two slots of [W 384 rows x 128 B | A 256 rows x 128 B], one vmcnt(0) and one
+    // barrier per two MFMA K-steps.  A DMA wave-instruction covers 8 rows x 128 B (whole lines), lane ->
+    // (row lane >> 3, chunk lane & 7); piece p = wave + 8 i holds rows 8 p .. 8 p + 7 at byte 1024 p.
+    constexpr int GA2 = kBM / 8 / kWaves, GW2 = kBN / 8 / kWaves, kOps2 = GA2 + GW2;  // 4 A + 6 W pieces
+    static_assert(kOps2 <= kNT, "two pieces ahead of each of the first MFMA pairs cover a stage's loads");
+    const int drow = lane >> 3, dpc = lane & 7;
+    // the XOR term of row 8 (wave + 8 i) + drow is ((wave & 1) << 2) | (drow >> 1) for every i
+    const int dsw = swz128(wave * 8 + drow, dpc) * 8;
+    uint32_t offA[GA2];
+#pragma unroll
+    for (int i = 0; i < GA2; ++i) {
+      const int r = (wave + kWaves * i) * 8 + drow;
+      const long gr = (m0 + r < ep.M) ? r : ep.M - 1 - m0;  // tail rows re-read row M-1, never stored
+      offA[i] = (uint32_t)(gr * lda + dsw);
+    }
+    const uint32_t offW = (uint32_t)((wave * 8 + drow) * ldw + dsw);  // piece i: + 64 i rows, wave-uniform
+    const int nk = K / 64;
+    // piece u (A pieces, then W pieces) of stage t, into slot t & 1
+    auto issue_op = [&](int t, int u) {
+      char* slot = smem + (t & 1) * kSlotBytes;
+      if (u < GA2)
+        __builtin_amdgcn_global_load_lds((gbl_void*)(A + (long)t * 64 + offA[u]),
+                                         (lds_void*)(slot + kWBytes2 + (wave + kWaves * u) * 1024), 16, 0, 0);
+      else
+        __builtin_amdgcn_global_load_lds((gbl_void*)(W + (long)t * 64 + (long)(u - GA2) * (kWaves * 8) * ldw + offW),
+                                         (lds_void*)(slot + (wave + kWaves * (u - GA2)) * 1024), 16, 0, 0);
+    };
+    // fragment read of K-step h: row = base16 + (lane & 15), logical chunk 4 h + (lane >> 4); the
+    // h = 1 address is the h = 0 address ^ 64
+    const int fl = (lane & 15) * 128 + (swz128(lane & 15, lane >> 4) << 4);
+    const int aoff = kWBytes2 + (wr * RW) * 128 + fl;
+    const int woff = (wn * kWN) * 128 + fl;
+
+#pragma unroll
+    for (int u = 0; u < kOps2; ++u) issue_op(0, u);
+    for (int t = 0; t < nk; ++t) {
+      // everything in flight is stage t (issued during iteration t - 1); past the barrier stage t is
+      // visible to every wave and every wave is done with stage t - 1's slot, which stage t + 1 enters
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      raw_barrier();
+      const char* bw = smem + (t & 1) * kSlotBytes;
+      // two passes of the 32-wide loop's six-pair body (K-step 2 t, then 2 t + 1): every accumulator
+      // sees ascending k.  The A fragments of the second pass replace the first pass's, each behind
+      // its last MFMAs in the sixth pair; stage t + 1's pieces go ahead of the first pairs.
+      bf16x8 af[MT], w0, w1, x0, x1;
+#pragma unroll
+      for (int i = 0; i < MT; ++i) af[i] = *(const bf16x8*)(bw + aoff + i * 16 * 128);
+      w0 = *(const bf16x8*)(bw + woff);
+      w1 = *(const bf16x8*)(bw + woff + 16 * 128);
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int q = 0; q < kNT; ++q) {
+        const int jp = q % (kNT / 2);
+        if (t + 1 < nk) {
+#pragma unroll
+          for (int u = 2 * q; u < 2 * q + 2; ++u)
+            if (u < kOps2) issue_op(t + 1, u);
+        }
+        if (q + 1 < kNT) {
+          const int h1 = (q + 1) / (kNT / 2), j1 = (q + 1) % (kNT / 2);
+          x0 = *(const bf16x8*)(bw + (woff ^ (h1 * 64)) + (2 * j1) * 16 * 128);
+          x1 = *(const bf16x8*)(bw + (woff ^ (h1 * 64)) + (2 * j1 + 1) * 16 * 128);
+        }
+#pragma unroll
+        for (int i = 0; i < MT; ++i) {
+          acc[i][2 * jp] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0, af[i], acc[i][2 * jp], 0, 0, 0);
+          acc[i][2 * jp + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1, af[i], acc[i][2 * jp + 1], 0, 0, 0);
+          if (q == kNT / 2 - 1) af[i] = *(const bf16x8*)(bw + (aoff ^ 64) + i * 16 * 128);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        w0 = x0;
+        w1 = x1;
+      }
+      __builtin_amdgcn_s_setprio(0);
+    }
   }
 
   // ---- epilogue, from registers ---------------------------------------------------------
@@ -315,18 +419,36 @@ __global__ __launch_bounds__(kThreads, 1) void k_gemm384(const uint16_t* __restr
   }
 }
 
-template <int MODE>
-int launch384(const uint16_t* A, long lda, const uint16_t* W, long ldw, long M, int N, int K, const Epi384& ep,
+// K per stage (NOMIC_GEMM384_BK): 64 where K is a multiple of 64, else and with 32 the 32-wide loop
+int g_bk = -1;
+int gemm384_bk() {
+  if (g_bk < 0) {
+    const char* e = getenv("NOMIC_GEMM384_BK");
+    g_bk = e && atoi(e) == 32 ? 32 : 64;
+  }
+  return g_bk;
+}
+
+template <int MODE, int BK>
+int launch384_bk(const uint16_t* A, long lda, const uint16_t* W, long ldw, long M, int N, int K, const Epi384& ep,
               hipStream_t s) {
+  constexpr int lds = BK == 64 ? kLdsBytes2 : kLdsBytes;
   static bool attr = [] {
-    (void)hipFuncSetAttribute((const void*)k_gemm384<MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
+    (void)hipFuncSetAttribute((const void*)k_gemm384<MODE, BK>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     return true;
   }();
   (void)attr;
   const int mtiles = (int)((M + kBM - 1) / kBM), ntiles = N / kBN;
-  hipLaunchKernelGGL(k_gemm384<MODE>, dim3(mtiles * ntiles), dim3(kThreads), kLdsBytes, s, A, lda, W, ldw, K, mtiles,
+  hipLaunchKernelGGL((k_gemm384<MODE, BK>), dim3(mtiles * ntiles), dim3(kThreads), lds, s, A, lda, W, ldw, K, mtiles,
                      ntiles, ep);
   return (int)hipGetLastError();
+}
+
+template <int MODE>
+int launch384(const uint16_t* A, long lda, const uint16_t* W, long ldw, long M, int N, int K, const Epi384& ep,
+              hipStream_t s) {
+  if (gemm384_bk() == 64 && K % 64 == 0) return launch384_bk<MODE, 64>(A, lda, W, ldw, M, N, K, ep, s);
+  return launch384_bk<MODE, 32>(A, lda, W, ldw, M, N, K, ep, s);
 }
 
 }  // namespace
@@ -357,3 +479,9 @@ int gemm384_launch(int mode, const uint16_t* A, long lda, const uint16_t* W, lon
 }
 
 }  // namespace spl
+
+extern "C" int nomic_gemm384_set_bk(int bk) {
+  const int prev = gemm384_bk();
+  g_bk = bk == 32 ? 32 : 64;
+  return prev;
+}

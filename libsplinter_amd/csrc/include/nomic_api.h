@@ -47,6 +47,10 @@ int nomic_row_stats(const float *part, int nparts, long M, float eps, float *st,
  * 256x256 phased kernel, 128 = 128x128 (where the shape allows; otherwise the next one that does).
  * Returns the previous setting. */
 int nomic_gemm_set_variant(int variant);
+/* K per LDS stage of the 256x384 kernel: 64 (default; env NOMIC_GEMM384_BK=32 turns it off) runs the
+ * 64-wide loop, one barrier per two MFMA K-steps, where K is a multiple of 64; 32, and any other K,
+ * run the 32-wide loop.  The output bits are the same.  Returns the previous setting. */
+int nomic_gemm384_set_bk(int bk);
 /* Tail split of the 256x256 kernel (default on; env NOMIC_GEMM_TAIL_SPLIT=0 turns it off): when the
  * last round of the grid would fill at most half the CUs (0 < tiles % CUs <= CUs / 2), its tiles
  * run as two 128-row half-tile workgroups each, in the same launch; the output bits do not change.

@@ -82,6 +82,8 @@ def _lib():
         L.nomic_row_stats.restype = c_int
         L.nomic_gemm_set_variant.argtypes = [c_int]
         L.nomic_gemm_set_variant.restype = c_int
+        L.nomic_gemm384_set_bk.argtypes = [c_int]
+        L.nomic_gemm384_set_bk.restype = c_int
         L.nomic_gemm_set_tail_split.argtypes = [c_int]
         L.nomic_gemm_set_tail_split.restype = c_int
         L.nomic_gemm256_grid.argtypes = [c_long, c_int]

@@ -2,7 +2,8 @@
 
   256s0 / 256s1   256^2 kernel, tail split off / on (nomic_gemm_set_tail_split)
   128             128^2 kernel
-  384             256x384 register-epilogue kernel (gemm384.hip)
+  384             256x384 register-epilogue kernel (gemm384.hip), stage width as the process has it
+  384k32 / 384k64 the same with 32- / 64-wide K stages (nomic_gemm384_set_bk)
 
 Default shape: the encoder's qkv projection with the RoPE epilogue (32768 x 2304 x 768).  The n-band
 of the tile order is a process-level knob: run once per NOMIC_GEMM_GN value for a band sweep.
@@ -17,7 +18,9 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-FORMS = {"256s0": (256, 0), "256s1": (256, 1), "128": (128, 1), "384": (384, 1)}  # (NOMIC_GEMM, tail split)
+# (NOMIC_GEMM, tail split, K per stage of the 256x384 kernel or 0 to leave it)
+FORMS = {"256s0": (256, 0, 0), "256s1": (256, 1, 0), "128": (128, 1, 0), "384": (384, 1, 0), "384k32": (384, 1, 32),
+         "384k64": (384, 1, 64)}
 
 
 def main():
@@ -46,9 +49,11 @@ def main():
     tab = torch.from_numpy(np.stack([np.cos(ang), np.sin(ang)], -1).astype(np.float32).reshape(8192, -1)).cuda()
 
     def run(f):
-        variant, split = FORMS[f]
+        variant, split, bk = FORMS[f]
         L.nomic_gemm_set_variant(variant)
         L.nomic_gemm_set_tail_split(split)
+        if bk:
+            L.nomic_gemm384_set_bk(bk)
         _chk(L.nomic_gemm(a.mode, x.data_ptr(), K, w.data_ptr(), K, M, N, K, outs[f].data_ptr(), ocols, None, 0,
                           tab.data_ptr(), pos.data_ptr(), N * 2 // 3 if a.mode == 3 else 0, _stream()), "gemm")
 

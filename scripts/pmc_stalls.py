@@ -5,7 +5,8 @@ SQ_ACTIVE_INST_VALU, SQ_VALU_MFMA_BUSY_CYCLES, SQ_BUSY_CYCLES, GRBM_GUI_ACTIVE).
 
 WAIT_ANY (parked on s_waitcnt / barrier) + WAIT_INST_ANY (issue stalls) + ACTIVE_INST_ANY ~= WAVE_CYCLES
 (MI355X_MICROARCH.md, rocprofv3 PMC slots).  MFMA busy = SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE / 8
-XCDs x 1024 SIMDs).
+XCDs x 1024 SIMDs).  GUI clock = GRBM_GUI_ACTIVE / 8 XCDs / dispatch time (it reads high on dispatches
+shorter than about 0.3 ms).
 
 python scripts/pmc_stalls.py COUNTER_COLLECTION.csv [--md] [--max-grid THREADS]
 
@@ -47,15 +48,15 @@ def main():
         agg[k]["_us"] += dur[d]
         agg[k]["_n"] += 1
     rows = sorted(agg.items(), key=lambda kv: -kv[1]["_us"])
-    print("| kernel | dispatches | µs avg | MFMA busy | wait (vmcnt/lgkm/barrier) | issue stall | of it LDS | active | active VALU |")
-    print("|---|---|---|---|---|---|---|---|---|")
+    print("| kernel | dispatches | µs avg | MFMA busy | wait (vmcnt/lgkm/barrier) | issue stall | of it LDS | active | active VALU | GUI clock GHz |")
+    print("|---|---|---|---|---|---|---|---|---|---|")
     for k, c in rows:
         w = c["SQ_WAVE_CYCLES"]
         busy = c.get("SQ_VALU_MFMA_BUSY_CYCLES", 0) / (c.get("GRBM_GUI_ACTIVE", 1) / 8 * 1024)
         f = lambda n: c.get(n, 0) / w * 100  # noqa: E731
         print(f"| `{k}` | {int(c['_n'])} | {c['_us'] / c['_n']:.1f} | {busy * 100:.1f} % | {f('SQ_WAIT_ANY'):.1f} % | "
               f"{f('SQ_WAIT_INST_ANY'):.1f} % | {f('SQ_WAIT_INST_LDS'):.1f} % | {f('SQ_ACTIVE_INST_ANY'):.1f} % | "
-              f"{f('SQ_ACTIVE_INST_VALU'):.1f} % |")
+              f"{f('SQ_ACTIVE_INST_VALU'):.1f} % | {c.get('GRBM_GUI_ACTIVE', 0) / 8 / (c['_us'] * 1e3):.2f} |")
     if "--md" not in sys.argv:
         return
 
