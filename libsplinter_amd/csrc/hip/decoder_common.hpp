@@ -1,5 +1,5 @@
 // decoder_common.hpp — helpers shared by decoder_kernels.hip (one generation) and decoder_batch.hip
-// (up to 16 generations per step): bf16 packing, wave reductions, the device state record, the
+// (up to 16 generations per step): wave reductions, the device state record, the
 // sampler's workspace layout and draw, the split-L geometry of the decode attention and the host's
 // shape dispatch.  The kernel bodies the two files share are in decoder_body_*.hpp.
 #pragma once
@@ -9,24 +9,9 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "bf16_util.hpp"
+
 namespace {
-
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float bf2f(uint32_t h16) { return __uint_as_float(h16 << 16); }
-__device__ __forceinline__ uint32_t pk2(float a, float b) {
-  const bf16x2_t v = {(__bf16)a, (__bf16)b};
-  return __builtin_bit_cast(uint32_t, v);
-}
-__device__ __forceinline__ void unpack8(uint4 v, float* f) {
-  f[0] = bf2f(v.x & 0xffff); f[1] = bf2f(v.x >> 16);
-  f[2] = bf2f(v.y & 0xffff); f[3] = bf2f(v.y >> 16);
-  f[4] = bf2f(v.z & 0xffff); f[5] = bf2f(v.z >> 16);
-  f[6] = bf2f(v.w & 0xffff); f[7] = bf2f(v.w >> 16);
-}
-__device__ __forceinline__ uint4 pack8(const float* f) {
-  return make_uint4(pk2(f[0], f[1]), pk2(f[2], f[3]), pk2(f[4], f[5]), pk2(f[6], f[7]));
-}
 
 // Device state of a generation (int32): [0] pos = tokens already in the KV cache, [1] token = the
 // token the next step consumes (the last sampled one), [2] step = sampler draws so far.  The batched

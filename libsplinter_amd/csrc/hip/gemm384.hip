@@ -15,14 +15,11 @@
 // so a lane's accumulator holds four CONSECUTIVE output columns of one row: k_gemm_rln's per-wave
 // layout and fragment read order.
 //
-// K loop, 32-wide stages (BK = 32; K % 64 != 0, or NOMIC_GEMM384_BK=32): k_gemm_rln's (gemm_rln.hip).  A
-// second copy: with the loop in a shared template hipcc spilled 35-40 registers in k_gemm_rln
-// (profiles/gemm384/README.md).  LDS rings of three W stages (384 x 32 bf16, 24 KB) and two A stages
-// (256 x 32, 16 KB), 104 KB; 2 A + 3 W LDS-DMA wave-instructions per wave per stage, issued two ahead of
-// each MFMA pair; counted vmcnt + one raw s_barrier per stage; 64-B rows with the 16-B chunk c of row r
-// stored at c ^ ((r >> 1) & 3), applied to the global source address and to the read address.  Ring
-// discipline: a staged slot is read only after the issuing wave's counted wait and a barrier the reader
-// has passed; a slot is restaged only after a barrier that follows its last read.
+// K loop, 32-wide stages (BK = 32; K % 64 != 0, or NOMIC_GEMM384_BK=32): the ring loop it shares with
+// k_gemm_rln, one text in gemm_ring32_issue.hpp + gemm_ring32_body.hpp, where the pipeline is explained.
+// Here: LDS rings of three W stages (384 x 32 bf16, 24 KB) and two A stages (256 x 32, 16 KB), 104 KB;
+// 2 A + 3 W LDS-DMA wave-instructions per wave per stage; 64-B rows with the 16-B chunk c of row r
+// stored at c ^ ((r >> 1) & 3), applied to the global source address and to the read address.
 //
 // K loop, 64-wide stages (BK = 64, the default where K % 64 == 0): two slots of [W 384 rows x 128 B |
 // A 256 rows x 128 B], 2 x 80 KB = 160 KB, so one s_waitcnt and one s_barrier per TWO MFMA K-steps (12
@@ -43,21 +40,16 @@
 // Epilogues run from registers, no LDS image.  pack_upgate and pack_qkv place up / gate and the NEOX
 // pair (d, d + 32) in n-tiles 2p and 2p + 1 at the same in-tile column, so SwiGLU and RoPE are
 // lane-local; lanes l and l ^ 16 hold adjacent 4-column groups of a row and exchange halves
-// (ds_swizzle, no LDS memory), so every store is one 16-B row piece.
+// (exchange16 in bf16_util.hpp: ds_swizzle, no LDS memory), so every store is one 16-B row piece.
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdlib>
 
+#include "bf16_util.hpp"
 #include "gemm_tile.hpp"
 #include "nomic_api.h"
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void gbl_void;
 
 constexpr int kBM = spl::kGemm384BM;  // rows per workgroup
 constexpr int kBN = spl::kGemm384BN;  // columns per workgroup
@@ -69,29 +61,12 @@ constexpr int kRowBytes = kBK * 2;            // 64
 constexpr int kABytes = kBM * kRowBytes;      // 16 KB per A stage
 constexpr int kWBytes = kBN * kRowBytes;      // 24 KB per W stage
 
-__device__ __forceinline__ uint32_t pk2(float a, float b) {
-  const bf16x2_t v = {(__bf16)a, (__bf16)b};
-  return __builtin_bit_cast(uint32_t, v);
-}
-
-__device__ __forceinline__ void raw_barrier() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-
 __device__ __forceinline__ void wait_vm(int n) {
   switch (n) {  // wave-uniform: a scalar branch to an immediate count
     case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
     default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
   }
 }
-
-// the value of lane ^ 16 (ds_swizzle bit mode: and 0x1f, or 0, xor 0x10)
-__device__ __forceinline__ uint32_t xor16(uint32_t v) { return (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x401F); }
-
-// physical 16-B chunk of logical chunk c in 64-B row r
-__device__ __forceinline__ int swz(int r, int c) { return c ^ ((r >> 1) & 3); }
 
 // NEOX rotation of one pair.  k_gemm256 / k_gemm_nt rotate 8 consecutive d per thread, and hipcc
 // contracts six of the eight: x1 = fma(a, c, -(b s)), x2 = fma(b, c, a s); the elements d = 6, 7
@@ -125,7 +100,7 @@ struct Epi384 {
   int gn;              // n-tiles per band of the tile order (spl::remap_tile)
 };
 
-// K pipeline: LDS rings of kNW W stages and kNA A stages, one barrier per stage (see k_gemm_rln).
+// K pipeline: LDS rings of kNW W stages and kNA A stages, one barrier per stage (gemm_ring32_body.hpp).
 // Measured and removed: rings of 4 W + 3 A stages (144 KB, counted waits 8 / 5 / 0): 280.6 against
 // 267.2 us on the SwiGLU shape, 122.0 against 114.2 us on the qkv shape (profiles/gemm384).
 constexpr int kNW = 3, kNA = 2;
@@ -139,14 +114,12 @@ constexpr int kWBytes2 = kBN * 128, kABytes2 = kBM * 128;  // 48 KB + 32 KB
 constexpr int kSlotBytes = kWBytes2 + kABytes2;
 constexpr int kLdsBytes2 = 2 * kSlotBytes;                 // 160 KB
 static_assert(kLdsBytes2 <= 160 * 1024, "LDS budget");
-__device__ __forceinline__ int swz128(int r, int c) { return c ^ ((r >> 1) & 7); }
 
 template <int MODE, int BK>
 __global__ __launch_bounds__(kThreads, 1) void k_gemm384(const uint16_t* __restrict__ A, long lda,
                                                          const uint16_t* __restrict__ W, long ldw, int K,
                                                          int mtiles, int ntiles, Epi384 ep) {
   constexpr int LW = kNW - 1, LA = kNA - 1;            // stages of lead
-  static_assert(LW > LA, "an iteration issues its A stage before its W stage");
   constexpr int kABase = kNW * kWBytes;                // LDS: [W ring | A ring]
   constexpr int kWaves = kThreads / 64;                // 8 waves: 4 (rows) x 2 (columns)
   constexpr int RW = kBM / 4, MT = RW / 16;            // rows and m-tiles per wave
@@ -184,73 +157,10 @@ __global__ __launch_bounds__(kThreads, 1) void k_gemm384(const uint16_t* __restr
       const int r = (wave + kWaves * i) * 16 + drow;
       offW[i] = (uint32_t)(r * ldw + swz(r, dpc) * 8);
     }
-    const int nk = K / kBK;
-    // ring slot of stage t: t % kNW (W), t % kNA (A) -- stages enter each ring in order
-    auto glds_w = [&](int t, int i) {
-      __builtin_amdgcn_global_load_lds((gbl_void*)(W + (long)t * kBK + offW[i]),
-                                       (lds_void*)(smem + (t % kNW) * kWBytes + (wave + kWaves * i) * 1024), 16, 0, 0);
-    };
-    auto glds_a = [&](int t, int i) {
-      __builtin_amdgcn_global_load_lds((gbl_void*)(A + (long)t * kBK + offA[i]),
-                                       (lds_void*)(smem + kABase + (t % kNA) * kABytes + (wave + kWaves * i) * 1024),
-                                       16, 0, 0);
-    };
-    // op u (0 .. GA+GW-1) of the loads iteration s issues: stage A(s + LA), then W(s + LW) (the
-    // counted wait at the top of an iteration relies on that order)
-    constexpr int kOps = GA + GW;
-    static_assert(kOps <= kNT, "two DMAs ahead of each of the kNT / 2 MFMA pairs cover a stage's loads");
-    auto issue_op = [&](int s, int u) {
-      const int tw = s + LW, ta = s + LA;
-      if (u < GA) { if (ta >= 0 && ta < nk) glds_a(ta, u); }
-      else if (tw >= 0 && tw < nk) glds_w(tw, u - GA);
-    };
-    auto issue = [&](int s) {
-#pragma unroll
-      for (int u = 0; u < kOps; ++u) issue_op(s, u);
-    };
-    // W(t + LW - 1) was issued after A(t): it may stay in flight at the top of iteration t
-    auto younger = [&](int t) -> int { return t + LW - 1 < nk ? GW : 0; };
-
-    // fragment read: row = base16 + (lane & 15), logical chunk lane >> 4
-    const int fl = (lane & 15) * kRowBytes + (swz(lane & 15, lane >> 4) << 4);
-    const int aoff = kABase + (wr * RW) * kRowBytes + fl;
-    const int woff = (wn * kWN) * kRowBytes + fl;
-
-    for (int s = -LW; s < 0; ++s) issue(s);
-    for (int t = 0; t < nk; ++t) {
-      wait_vm(younger(t));
-      raw_barrier();  // stage t visible to every wave; every wave is done with stage t-1's slots
-      const char* bw = smem + (t % kNW) * kWBytes;
-      const char* ba = smem + (t % kNA) * kABytes;
-      // A fragments for the whole stage, W fragments two n-tiles at a time with the next pair's reads
-      // issued ahead of the current pair's MFMAs (sched_barrier pins the pairs); the stage's five DMAs
-      // go two ahead of each of the first MFMA pairs, in issue order.
-      bf16x8 af[MT], w0, w1, x0, x1;
-#pragma unroll
-      for (int i = 0; i < MT; ++i) af[i] = *(const bf16x8*)(ba + aoff + i * 16 * kRowBytes);
-      w0 = *(const bf16x8*)(bw + woff);
-      w1 = *(const bf16x8*)(bw + woff + 16 * kRowBytes);
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int jp = 0; jp < kNT / 2; ++jp) {
-#pragma unroll
-        for (int u = 2 * jp; u < 2 * jp + 2; ++u)
-          if (u < kOps) issue_op(t, u);
-        if (jp + 1 < kNT / 2) {
-          x0 = *(const bf16x8*)(bw + woff + (2 * (jp + 1)) * 16 * kRowBytes);
-          x1 = *(const bf16x8*)(bw + woff + (2 * (jp + 1) + 1) * 16 * kRowBytes);
-        }
-#pragma unroll
-        for (int i = 0; i < MT; ++i) {
-          acc[i][2 * jp] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0, af[i], acc[i][2 * jp], 0, 0, 0);
-          acc[i][2 * jp + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1, af[i], acc[i][2 * jp + 1], 0, 0, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        w0 = x0;
-        w1 = x1;
-      }
-      __builtin_amdgcn_s_setprio(0);
-    }
+#define GEMM_RING32_STAGE_HOOK(t)
+#include "gemm_ring32_issue.hpp"
+#include "gemm_ring32_body.hpp"
+#undef GEMM_RING32_STAGE_HOOK
   } else {
     // ---- 64-wide stages: two slots of [W 384 rows x 128 B | A 256 rows x 128 B], one vmcnt(0) and one
     // barrier per two MFMA K-steps.  A DMA wave-instruction covers 8 rows x 128 B (whole lines), lane ->
@@ -338,10 +248,9 @@ __global__ __launch_bounds__(kThreads, 1) void k_gemm384(const uint16_t* __restr
   const bool odd = (lane >> 4) & 1;
   const int h8 = (lane >> 5) * 8;          // the lane's 8 columns inside a 16-wide n-tile
   const long mb = m0 + wr * RW + rl;       // row of m-tile i: mb + 16 i
-  auto exchange = [&](const uint32_t (&x)[2], const uint32_t (&y)[2]) -> uint4 {
-    const uint32_t gx = xor16(odd ? x[0] : y[0]), gy = xor16(odd ? x[1] : y[1]);
-    return odd ? make_uint4(gx, gy, y[0], y[1]) : make_uint4(x[0], x[1], gx, gy);
-  };
+  // through a lambda that captures `odd`: called directly, exchange16 changes the code of this kernel
+  // (the lane-group test becomes a 32-bit compare and registers move)
+  auto exchange = [&](const uint32_t (&x)[2], const uint32_t (&y)[2]) -> uint4 { return exchange16(odd, x, y); };
   if constexpr (MODE == NOMIC_EPI_STORE) {
     uint16_t* o = ep.out + n0 + wn * kWN + (odd ? 16 : 0) + h8;  // + 32 p: n-tiles 2p, 2p + 1
 #pragma unroll
@@ -433,11 +342,7 @@ template <int MODE, int BK>
 int launch384_bk(const uint16_t* A, long lda, const uint16_t* W, long ldw, long M, int N, int K, const Epi384& ep,
               hipStream_t s) {
   constexpr int lds = BK == 64 ? kLdsBytes2 : kLdsBytes;
-  static bool attr = [] {
-    (void)hipFuncSetAttribute((const void*)k_gemm384<MODE, BK>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    return true;
-  }();
-  (void)attr;
+  spl::allow_lds<k_gemm384<MODE, BK>>(lds);
   const int mtiles = (int)((M + kBM - 1) / kBM), ntiles = N / kBN;
   hipLaunchKernelGGL((k_gemm384<MODE, BK>), dim3(mtiles * ntiles), dim3(kThreads), lds, s, A, lda, W, ldw, K, mtiles,
                      ntiles, ep);

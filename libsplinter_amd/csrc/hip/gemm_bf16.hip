@@ -16,36 +16,25 @@
 // Epilogue: accumulators go through LDS in fp32, then each thread owns
 // 16-B output chunks, so every fused epilogue (residual add, SwiGLU, RoPE)
 // works on whole rows with vector loads/stores.
+// Shared with gemm384.hip and gemm_rln.hip: the bf16 and lane helpers (bf16_util.hpp), the tile order,
+// SwiGLU and allow_lds (gemm_tile.hpp).
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdlib>
 #include <type_traits>
 
+#include "bf16_util.hpp"
 #include "gemm_tile.hpp"
 #include "glds_asm.hpp"
 #include "nomic_api.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void gbl_void;
-
 constexpr int BM = 128, BN = 128, BK = 64;
 constexpr int kThreads = 256;
 constexpr int kTileBytes = BM * BK * 2;            // 16 KB per operand tile
 constexpr int kEpiStride = BN + 4;                 // fp32 epilogue row stride (floats)
 constexpr int kLdsBytes = (BM * kEpiStride * 4 > 4 * kTileBytes) ? BM * kEpiStride * 4 : 4 * kTileBytes;
-
-__device__ __forceinline__ float bf2f(uint16_t h) { return __uint_as_float((uint32_t)h << 16); }
-// fp32 -> bf16, round-to-nearest-even, on the hardware converter (v_cvt_pk_bf16_f32: one
-// instruction per PAIR via pk2, instead of a 5-op integer rounding sequence per value)
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t pk2(float a, float b) {
-  const bf16x2_t v = {(__bf16)a, (__bf16)b};
-  return __builtin_bit_cast(uint32_t, v);
-}
 
 // Stage one BMxBK tile of a K-contiguous matrix (row stride ld elements)
 // starting at (row0, k0) into the lane-linear LDS image at `dst`.
@@ -422,21 +411,6 @@ __device__ __forceinline__ void wait_vm(int n) {
     case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
     default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
   }
-}
-
-__device__ __forceinline__ void raw_barrier() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-
-__device__ __forceinline__ uint4 pack8(const float* v) {
-  uint4 o;
-  o.x = pk2(v[0], v[1]);
-  o.y = pk2(v[2], v[3]);
-  o.z = pk2(v[4], v[5]);
-  o.w = pk2(v[6], v[7]);
-  return o;
 }
 
 // The LDS-DMAs are issued from inline asm (glds_asm.hpp): with the builtin, hipcc put lgkmcnt(0)
@@ -818,11 +792,6 @@ int split_tiles(long T) {
   return tail_split() && R > 0 && R <= cus / 2 ? R : 0;
 }
 
-template <typename F>
-void allow_lds(F* f, int bytes) {
-  (void)hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-}
-
 // Kernel choice (NOMIC_GEMM): 0 = auto, 128 = the 128^2 kernel, 256 = the 256^2 kernel, 384 = the
 // 256x384 register-epilogue kernel (gemm384.hip; STORE / SWIGLU / ROPE with N % 384 == 0).
 //
@@ -910,11 +879,7 @@ int launch(const uint16_t* A, long lda, const uint16_t* W, long ldw, long M, int
     return e && atol(e) > 0 ? atol(e) : 1024L;
   }();
   if (k256_ok && fits && (var == 256 || (var == 0 && tiles256 >= min_tiles))) {
-    static bool attr = [] {
-      allow_lds(k_gemm256<MODE>, kLds2SplitBytes);
-      return true;
-    }();
-    (void)attr;
+    spl::allow_lds<k_gemm256<MODE>>(kLds2SplitBytes);
     const int mtiles = (int)(mpad / 256), ntiles = N / 256;
     ep.gn = band_width(ntiles, 4);
     ep.nsplit = split_tiles(tiles256);

@@ -19,7 +19,8 @@
 // K loop: BK = 32 (one MFMA k-step), LDS rings of three W stages (768 x 32 bf16, 48 KB each) and
 // two A stages (128 x 32, 8 KB each), filled by global_load_lds_dwordx4 (LDS-DMA; 7
 // wave-instructions per wave per stage) two and one stages ahead of the MFMAs and issued between
-// them, counted vmcnt + raw s_barrier (no vmcnt(0) drain in the loop).  The
+// them, counted vmcnt + raw s_barrier (no vmcnt(0) drain in the loop): the ring loop shared with
+// k_gemm384's 32-wide arm, one text in gemm_ring32_issue.hpp + gemm_ring32_body.hpp.  The
 // LDS image has 64-byte rows; the 16-byte chunk c of row r is stored at chunk c ^ ((r >> 1) & 3),
 // which makes every ds_read_b128 lane group (16 lanes) hit 16 distinct bank slots (brute-forced
 // over the gfx950 b128 lane groups); glds writes lane-linearly, so the XOR is applied to the
@@ -32,15 +33,11 @@
 #include <cstdint>
 #include <cstdlib>
 
+#include "bf16_util.hpp"
+#include "gemm_tile.hpp"
 #include "nomic_api.h"
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void gbl_void;
 
 constexpr int kBM = 128;          // rows per workgroup
 constexpr int kN = 768;           // output width (= model width)
@@ -53,25 +50,11 @@ constexpr int kABytes = kBM * kRowBytes;             // 8 KB per A stage
 constexpr int kWBytes = kN * kRowBytes;              // 48 KB per W stage
 constexpr int kEpiLds = 4 * kBM * 4;                 // epilogue: [4 column waves][128 rows] fp32 row sums
 
-// K pipeline: LDS rings of kNW W stages and kNA A stages, one barrier per stage.  Iteration t,
-// after its barrier, issues the stages A(t + kNA - 1) and W(t + kNW - 1) into ring slots last read
-// in iteration t-1, then computes stage t: W -- L2-resident, re-read by every workgroup -- runs two
-// stages ahead, A -- streamed from HBM, read once -- one.
+// K pipeline: LDS rings of kNW W stages and kNA A stages, one barrier per stage; the loop and its
+// explanation are in gemm_ring32_body.hpp.
 constexpr int kNW = 3, kNA = 2;
 constexpr int kLdsBytes = kNW * kWBytes + kNA * kABytes;  // 160 KB: [W ring | A ring]
 static_assert(kLdsBytes <= 160 * 1024 && kLdsBytes >= kEpiLds, "LDS budget");
-
-__device__ __forceinline__ float bf2f(uint32_t h16) { return __uint_as_float(h16 << 16); }
-__device__ __forceinline__ uint32_t pk2(float a, float b) {
-  const bf16x2_t v = {(__bf16)a, (__bf16)b};
-  return __builtin_bit_cast(uint32_t, v);
-}
-
-__device__ __forceinline__ void raw_barrier() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
 
 __device__ __forceinline__ void wait_vm(int n) {
   switch (n) {  // wave-uniform: a scalar branch to an immediate count
@@ -79,13 +62,6 @@ __device__ __forceinline__ void wait_vm(int n) {
     default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
   }
 }
-
-// the value of lane ^ 16 (ds_swizzle bit mode: and 0x1f, or 0, xor 0x10 -- a cross-lane move
-// on the LDS crossbar that touches no LDS memory)
-__device__ __forceinline__ uint32_t xor16(uint32_t v) { return (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x401F); }
-
-// physical 16-B chunk of logical chunk c in 64-B row r
-__device__ __forceinline__ int swz(int r, int c) { return c ^ ((r >> 1) & 3); }
 
 // EPI 0: residual added in the epilogue (8-B loads).  3 (K = 768, the o-proj): the residual is
 // added during the K loop -- stage t loads the lane's residual pieces of two of its 48 (m-tile,
@@ -124,7 +100,6 @@ __global__ __launch_bounds__(kThreads, 1) void k_gemm_rln(const uint16_t* __rest
                                                           const uint16_t* __restrict__ beta, float eps,
                                                           uint16_t* out, long ldo) {
   constexpr int LW = kNW - 1, LA = kNA - 1;            // stages of lead
-  static_assert(LW > LA, "an iteration issues its A stage before its W stage");
   constexpr int kABase = kNW * kWBytes;                // LDS: [W ring | A ring]
   constexpr int kWaves = kThreads / 64;                // 8 waves: 2 (rows) x 4 (columns)
   constexpr int RW = kBM / 2, MT = RW / 16;            // rows and m-tiles per wave
@@ -154,44 +129,14 @@ __global__ __launch_bounds__(kThreads, 1) void k_gemm_rln(const uint16_t* __rest
     const int r = (wave + kWaves * i) * 16 + drow;
     offW[i] = (uint32_t)(r * ldw + swz(r, dpc) * 8);
   }
-  const int nk = K / kBK;
-  // ring slot of stage t: t % kNW (W), t % kNA (A) -- stages enter each ring in order
-  auto glds_w = [&](int t, int i) {
-    __builtin_amdgcn_global_load_lds((gbl_void*)(W + (long)t * kBK + offW[i]),
-                                     (lds_void*)(smem + (t % kNW) * kWBytes + (wave + kWaves * i) * 1024), 16, 0, 0);
-  };
-  auto glds_a = [&](int t, int i) {
-    __builtin_amdgcn_global_load_lds((gbl_void*)(A + (long)t * kBK + offA[i]),
-                                     (lds_void*)(smem + kABase + (t % kNA) * kABytes + (wave + kWaves * i) * 1024),
-                                     16, 0, 0);
-  };
-  // op u (0 .. GA+GW-1) of the loads iteration s issues: stage A(s + LA), then W(s + LW) (the
-  // counted wait at the top of an iteration relies on that order)
-  constexpr int kOps = GA + GW;
-  static_assert(kOps <= kNT, "two DMAs ahead of each of the kNT / 2 MFMA pairs cover a stage's loads");
-  auto issue_op = [&](int s, int u) {
-    const int tw = s + LW, ta = s + LA;
-    if (u < GA) { if (ta >= 0 && ta < nk) glds_a(ta, u); }
-    else if (tw >= 0 && tw < nk) glds_w(tw, u - GA);
-  };
-  auto issue = [&](int s) {
-#pragma unroll
-    for (int u = 0; u < kOps; ++u) issue_op(s, u);
-  };
-  // W(t + LW - 1) was issued after A(t): it may stay in flight at the top of iteration t
-  auto younger = [&](int t) -> int { return t + LW - 1 < nk ? GW : 0; };
-
-  // fragment read: row = base16 + (lane & 15), logical chunk lane >> 4
-  const int fl = (lane & 15) * kRowBytes + (swz(lane & 15, lane >> 4) << 4);
-  const int aoff = kABase + (wr * RW) * kRowBytes + fl;
-  const int woff = (wn * kWN) * kRowBytes + fl;
-
+#include "gemm_ring32_issue.hpp"
+  // the accumulators and the EPI 3 state are declared here, between the two halves of the ring text:
+  // declared ahead of the DMA lambdas they change the register allocation of all three forms
   f32x4 acc[MT][kNT];
 #pragma unroll
   for (int i = 0; i < MT; ++i)
 #pragma unroll
     for (int j = 0; j < kNT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  for (int s = -LW; s < 0; ++s) issue(s);
   // EPI 3: residual pieces of accumulator tile u = (u / kNT, u % kNT), two tiles per stage
   const long rmb = m0 + wr * RW + (lane & 15);
   const int rcq = (lane >> 4) * 4;
@@ -208,57 +153,25 @@ __global__ __launch_bounds__(kThreads, 1) void k_gemm_rln(const uint16_t* __rest
     acc[i][j][2] += bf2f(rr.y & 0xffff);
     acc[i][j][3] += bf2f(rr.y >> 16);
   };
-  for (int t = 0; t < nk; ++t) {
-    wait_vm(younger(t));
-    raw_barrier();  // stage t visible to every wave; every wave is done with stage t-1's slots
-    if (KRES && t < 24) {
-      // loaded one stage ahead of their add, issued before this stage's DMAs (older than them: the
-      // counted waits above stay exact); a chain of uniform branches keeps the tile indices static
-#pragma unroll
-      for (int k = 0; k < 24; ++k) {
-        if (t == k) {
-          if (k > 0) {
-            res_add(2 * (k - 1), rq[0]);
-            res_add(2 * (k - 1) + 1, rq[1]);
-          }
-          res_load(2 * k, rq[0]);
-          res_load(2 * k + 1, rq[1]);
-        }
-      }
-    }
-    const char* bw = smem + (t % kNW) * kWBytes;
-    const char* ba = smem + (t % kNA) * kABytes;
-    // A fragments for the whole stage, W fragments two n-tiles at a time with the next pair's reads
-    // issued ahead of the current pair's MFMAs (sched_barrier pins the pairs: hoisting all 12 W
-    // reads would need 48 more registers than the 256 two waves per SIMD allow).  The stage's seven
-    // DMAs go two ahead of each MFMA pair, in issue order: issued together after the barrier they
-    // held both waves of a SIMD off the matrix core for the ~100-cycle issue cost of each.
-    bf16x8 af[MT], w0, w1, x0, x1;
-#pragma unroll
-    for (int i = 0; i < MT; ++i) af[i] = *(const bf16x8*)(ba + aoff + i * 16 * kRowBytes);
-    w0 = *(const bf16x8*)(bw + woff);
-    w1 = *(const bf16x8*)(bw + woff + 16 * kRowBytes);
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int jp = 0; jp < kNT / 2; ++jp) {
-#pragma unroll
-      for (int u = 2 * jp; u < 2 * jp + 2; ++u)
-        if (u < kOps) issue_op(t, u);
-      if (jp + 1 < kNT / 2) {
-        x0 = *(const bf16x8*)(bw + woff + (2 * (jp + 1)) * 16 * kRowBytes);
-        x1 = *(const bf16x8*)(bw + woff + (2 * (jp + 1) + 1) * 16 * kRowBytes);
-      }
-#pragma unroll
-      for (int i = 0; i < MT; ++i) {
-        acc[i][2 * jp] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0, af[i], acc[i][2 * jp], 0, 0, 0);
-        acc[i][2 * jp + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1, af[i], acc[i][2 * jp + 1], 0, 0, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      w0 = x0;
-      w1 = x1;
-    }
-    __builtin_amdgcn_s_setprio(0);
+  // stage t, between its barrier and its MFMAs: the pieces are loaded one stage ahead of their add,
+  // issued before this stage's DMAs (older than them: the counted waits stay exact); a chain of
+  // uniform branches keeps the tile indices static.  Text, not a lambda: as a lambda it changes the
+  // register allocation of all three forms.
+#define GEMM_RING32_STAGE_HOOK(t)                      \
+  if (KRES && t < 24) {                                \
+    _Pragma("unroll") for (int k = 0; k < 24; ++k) {   \
+      if (t == k) {                                    \
+        if (k > 0) {                                   \
+          res_add(2 * (k - 1), rq[0]);                 \
+          res_add(2 * (k - 1) + 1, rq[1]);             \
+        }                                              \
+        res_load(2 * k, rq[0]);                        \
+        res_load(2 * k + 1, rq[1]);                    \
+      }                                                \
+    }                                                  \
   }
+#include "gemm_ring32_body.hpp"
+#undef GEMM_RING32_STAGE_HOOK
   if constexpr (KRES) {  // the last pair (loaded at stage 23)
     res_add(46, rq[0]);
     res_add(47, rq[1]);
@@ -290,9 +203,10 @@ __global__ __launch_bounds__(kThreads, 1) void k_gemm_rln(const uint16_t* __rest
         for (int i = 0; i < MT; ++i) {
           const long m = mb + 16 * i < M ? mb + 16 * i : M - 1;
           const uint4 rr = *(const uint4*)(res + m * ldr + c8 + 32 * p);
-          const uint32_t gx = xor16(odd ? rr.x : rr.z), gy = xor16(odd ? rr.y : rr.w);
-          const uint32_t r0[2] = {odd ? gx : rr.x, odd ? gy : rr.y};  // tile 2p
-          const uint32_t r1[2] = {odd ? rr.z : gx, odd ? rr.w : gy};  // tile 2p + 1
+          const uint32_t lo[2] = {rr.x, rr.y}, hi[2] = {rr.z, rr.w};
+          const uint4 rv = exchange16(odd, lo, hi);
+          const uint32_t r0[2] = {rv.x, rv.y};  // tile 2p
+          const uint32_t r1[2] = {rv.z, rv.w};  // tile 2p + 1
 #pragma unroll
           for (int h = 0; h < 2; ++h) {
             const int j = 2 * p + h;
@@ -392,8 +306,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_gemm_rln(const uint16_t* __rest
             pk[h][1] = pk2(o[2], o[3]);
           }
           // the even group keeps tile 2p and gets the partner's four columns of it, the odd group 2p + 1
-          const uint32_t gx = xor16(odd ? pk[0][0] : pk[1][0]), gy = xor16(odd ? pk[0][1] : pk[1][1]);
-          const uint4 v = odd ? make_uint4(gx, gy, pk[1][0], pk[1][1]) : make_uint4(pk[0][0], pk[0][1], gx, gy);
+          const uint4 v = exchange16(odd, pk[0], pk[1]);
           if (m < M) *(uint4*)(out + m * ldo + c8 + 32 * p) = v;
         }
       }
@@ -438,11 +351,7 @@ template <int EPI>
 void launch_rln(unsigned blocks, hipStream_t s, const uint16_t* A, long lda, const uint16_t* W, long ldw, int K, long M,
                 const uint16_t* res, long ldr, const uint16_t* gamma, const uint16_t* beta, float eps, uint16_t* out,
                 long ldo) {
-  static bool attr = [] {
-    (void)hipFuncSetAttribute((const void*)k_gemm_rln<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-    return true;
-  }();
-  (void)attr;
+  spl::allow_lds<k_gemm_rln<EPI>>(kLdsBytes);
   hipLaunchKernelGGL(k_gemm_rln<EPI>, dim3(blocks), dim3(kThreads), kLdsBytes, s, A, lda, W, ldw, K, M, res, ldr, gamma,
                      beta, eps, out, ldo);
 }

@@ -1,6 +1,7 @@
 // gemm_tile.hpp — what the encoder GEMM files share: the block -> tile order, the SwiGLU formula,
-// and the entry of the 256x384 register-epilogue kernel (gemm384.hip) that gemm_bf16.hip's launcher
-// dispatches to.
+// the dynamic-LDS limit of a kernel, and the entry of the 256x384 register-epilogue kernel
+// (gemm384.hip) that gemm_bf16.hip's launcher dispatches to.  The bf16 and lane helpers are in
+// bf16_util.hpp, the 32-wide ring K loop of k_gemm_rln and k_gemm384 in gemm_ring32_body.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -25,6 +26,16 @@ __device__ __forceinline__ void remap_tile(int bid, int nb, int nt, int gn, int&
 // sequence in the epilogue; ~1 ulp, far below the bf16 output rounding)
 __device__ __forceinline__ float swiglu(float up, float g) {
   return up * g * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-g * 1.4426950408889634f));
+}
+
+// host: raise kernel F's dynamic-LDS limit to `bytes`, once per kernel
+template <auto F>
+void allow_lds(int bytes) {
+  static const bool once = [bytes] {
+    (void)hipFuncSetAttribute((const void*)F, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    return true;
+  }();
+  (void)once;
 }
 
 // 256x384 kernel (gemm384.hip).  gemm384_ok: the shapes, strides and alignments it takes (mode is a

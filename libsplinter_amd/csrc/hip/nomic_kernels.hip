@@ -12,33 +12,12 @@
 #include <cstdint>
 
 #include "arena_dev.hpp"
+#include "bf16_util.hpp"
 #include "nomic_api.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int D = 768;
-
-__device__ __forceinline__ float bf2f(uint32_t h16) { return __uint_as_float(h16 << 16); }
-// fp32 -> bf16 (RNE) on the hardware converter: v_cvt_pk_bf16_f32, one instruction per pair (pk2)
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t f2bf(float f) { return __builtin_bit_cast(uint16_t, (__bf16)f); }
-__device__ __forceinline__ uint32_t pk2(float a, float b) {
-  const bf16x2_t v = {(__bf16)a, (__bf16)b};
-  return __builtin_bit_cast(uint32_t, v);
-}
-__device__ __forceinline__ void unpack8(uint4 v, float* f) {
-  f[0] = bf2f(v.x & 0xffff); f[1] = bf2f(v.x >> 16);
-  f[2] = bf2f(v.y & 0xffff); f[3] = bf2f(v.y >> 16);
-  f[4] = bf2f(v.z & 0xffff); f[5] = bf2f(v.z >> 16);
-  f[6] = bf2f(v.w & 0xffff); f[7] = bf2f(v.w >> 16);
-}
-__device__ __forceinline__ uint4 pack8(const float* f) {
-  return make_uint4(pk2(f[0], f[1]), pk2(f[2], f[3]),
-                    pk2(f[4], f[5]), pk2(f[6], f[7]));
-}
 
 // ------------------------------------------------------------ LayerNorm --
 // 32 lanes per row (half a wave), 24 elements = 3 x 16-B per lane; two-pass

@@ -205,9 +205,9 @@ def fold_ln(w: torch.Tensor, g: torch.Tensor, b: torch.Tensor):
 
 
 class NomicWeights:
-    """Device-resident bf16 weights in kernel layout (plus the LN-folded copies the fused
-    forward uses: ``wqkv_f`` folds the previous layer's output LN, ``wupgate_f`` this layer's
-    attention-output LN)."""
+    """Device-resident bf16 weights in kernel layout.  The LN-folded copies that only the "folded"
+    schedule reads (``wqkv_f`` folds the previous layer's output LN, ``wupgate_f`` this layer's
+    attention-output LN) are built by the first ``folded()`` call."""
 
     def __init__(self, cfg: NomicConfig, tensors: Dict[str, torch.Tensor], device="cuda"):
         self.cfg = cfg
@@ -224,11 +224,18 @@ class NomicWeights:
                 "wdown": bf(t["wdown"]),
                 "ln1_g": bf(t["ln1_g"]), "ln1_b": bf(t["ln1_b"]), "ln2_g": bf(t["ln2_g"]), "ln2_b": bf(t["ln2_b"]),
             })
+
+    def folded(self):
+        """The layer dicts with the LN-folded copies and their fp32 constants added (built once, about
+        13 MB per layer at the shipped shape)."""
         for i, lw in enumerate(self.layers):
+            if "wupgate_f" in lw:
+                continue
             lw["wupgate_f"], lw["ug_c1"], lw["ug_c2"] = fold_ln(lw["wupgate"], lw["ln1_g"], lw["ln1_b"])
             if i > 0:
                 prev = self.layers[i - 1]
                 lw["wqkv_f"], lw["qkv_c1"], lw["qkv_c2"] = fold_ln(lw["wqkv"], prev["ln2_g"], prev["ln2_b"])
+        return self.layers
 
     @classmethod
     def from_numpy(cls, cfg, weights: Dict[str, np.ndarray], device="cuda"):
@@ -377,41 +384,76 @@ class NomicEncoder:
         ang = np.arange(npos, dtype=np.float64)[:, None] * inv[None, :]
         tab = np.stack([np.cos(ang), np.sin(ang)], axis=-1).astype(np.float32)
         self.rope = torch.from_numpy(tab.reshape(npos, -1)).cuda()
-        self._ws_tokens = 0
+        self._ws_tokens, self._ws_schedule = 0, None
+        self.h = self.h2 = self.part1 = self.part2 = None
+        self._scale = 1.0 / math.sqrt(cfg.head_dim)
         self._ensure(max_tokens)
 
     def _ensure(self, T_pad: int):
-        if T_pad <= self._ws_tokens:
+        """Workspaces of at least T_pad rows for the schedule in force: x, attn, qkv and ffn for every
+        schedule, h for "split" and "folded", h2 and the row-statistics partials for "folded" only,
+        so the default schedule does not pay for the opt-in ones."""
+        if T_pad <= self._ws_tokens and self._ws_schedule == self.schedule:
             return
         cfg = self.cfg
-        e = dict(dtype=torch.bfloat16, device="cuda")
-        self.x = torch.empty((T_pad, cfg.d), **e)
-        self.h = torch.empty((T_pad, cfg.d), **e)
-        self.attn = torch.empty((T_pad, cfg.d), **e)
-        self.qkv = torch.empty((T_pad, 3 * cfg.d), **e)
-        self.ffn = torch.empty((T_pad, cfg.ffn), **e)
-        self.h2 = torch.empty((T_pad, cfg.d), **e)
-        f = dict(dtype=torch.float32, device="cuda")
-        self.part1 = torch.empty((T_pad, 2 * (cfg.d // 128)), **f)  # (mean, M2) per 128 columns of h1
-        self.part2 = torch.empty((T_pad, 2 * (cfg.d // 128)), **f)  # ... of h2
-        self._ws_tokens = T_pad
+        bf, f32 = torch.bfloat16, torch.float32
+        want = {"x": (cfg.d, bf), "attn": (cfg.d, bf), "qkv": (3 * cfg.d, bf), "ffn": (cfg.ffn, bf)}
+        if self.schedule in ("split", "folded"):
+            want["h"] = (cfg.d, bf)
+        if self.schedule == "folded":
+            want["h2"] = (cfg.d, bf)
+            want["part1"] = (2 * (cfg.d // 128), f32)  # (mean, M2) per 128 columns of h1
+            want["part2"] = (2 * (cfg.d // 128), f32)  # ... of h2
+        rows = max(T_pad, self._ws_tokens)
+        for name, (cols, dtype) in want.items():
+            t = getattr(self, name, None)
+            if t is None or t.shape[0] < rows:
+                setattr(self, name, torch.empty((rows, cols), dtype=dtype, device="cuda"))
+        self._ws_tokens, self._ws_schedule = rows, self.schedule
 
-    def _gemm(self, mode, A, W, M, out, res=None, pos=None):
+    # Every launch takes the stream handle `s` it runs on: the NOMIC_SPLIT groups pass their own.
+    def _gemm(self, mode, A, W, M, out, s, res=None, pos=None):
         N_, K = W.shape
         _chk(self.L.nomic_gemm(mode, A.data_ptr(), A.stride(0), W.data_ptr(), W.stride(0), M,
                                N_, K, out.data_ptr(), out.stride(0), res.data_ptr() if res is not None else None,
                                res.stride(0) if res is not None else 0, self.rope.data_ptr(),
-                               pos.data_ptr() if pos is not None else None, 2 * self.cfg.d, _stream()), "gemm")
+                               pos.data_ptr() if pos is not None else None, 2 * self.cfg.d, s), "gemm")
 
-    def _gemm_ln(self, mode, A, W, M, out, res=None, pos=None, pin=None, c1=None, c2=None, ln=None, part=None):
+    def _gemm_ln(self, mode, A, W, M, out, s, res=None, pos=None, pin=None, c1=None, c2=None, ln=None, part=None):
         N_, K = W.shape
         ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
         _chk(self.L.nomic_gemm_ln(mode, A.data_ptr(), A.stride(0), W.data_ptr(), W.stride(0), M, N_, K,
                                   out.data_ptr(), out.stride(0), ptr(res), res.stride(0) if res is not None else 0,
                                   self.rope.data_ptr(), ptr(pos), 2 * self.cfg.d, ptr(pin),
                                   pin.shape[1] // 2 if pin is not None else 0, self.cfg.eps, ptr(c1), ptr(c2),
-                                  ptr(ln[0]) if ln else None, ptr(ln[1]) if ln else None, ptr(part), _stream()),
+                                  ptr(ln[0]) if ln else None, ptr(ln[1]) if ln else None, ptr(part), s),
              f"gemm_ln({mode})")
+
+    def _res_ln(self, A, W, M, x, g, beta, s):
+        """x[:M] = LN(A W^T + x) * g + beta in place (row-complete MFMA kernel, gemm_rln.hip)."""
+        N_, K = W.shape
+        _chk(self.L.nomic_gemm_res_ln(A.data_ptr(), A.stride(0), W.data_ptr(), W.stride(0), M, N_, K, x.data_ptr(),
+                                      x.stride(0), g.data_ptr(), beta.data_ptr(), self.cfg.eps, x.data_ptr(),
+                                      x.stride(0), s), "gemm_res_ln")
+
+    def _layernorm(self, h, T, g, beta, x, s, what):
+        _chk(self.L.nomic_layernorm(h.data_ptr(), T, g.data_ptr(), beta.data_ptr(), self.cfg.eps, x.data_ptr(), s),
+             what)
+
+    def _embed_ln(self, b: Batch, x, s):
+        w = self.w
+        _chk(self.L.nomic_embed_ln(b.ids.data_ptr(), b.T, w.tok.data_ptr(), w.type_row.data_ptr(), w.emb_g.data_ptr(),
+                                   w.emb_b.data_ptr(), self.cfg.eps, x.data_ptr(), s), "embed_ln")
+
+    def _attention(self, b: Batch, qkv, attn, s):
+        _chk(self.L.nomic_attention(qkv.data_ptr(), attn.data_ptr(), b.cu.data_ptr(), b.qblocks.data_ptr(), b.nqb,
+                                    self.cfg.heads, self._scale, s), "attention")
+
+    def _begin(self, b: Batch):
+        """What every forward starts with: the length check and the workspaces; the current stream's handle."""
+        assert b.max_len <= self.rope.shape[0]
+        self._ensure(b.T_pad)
+        return _stream()
 
     # Schedules of the post-LN layers (K15 / K16-down), all on hand-written kernels:
     #   "fused"  (default) residual GEMM + residual add + LayerNorm in one row-complete kernel
@@ -429,78 +471,48 @@ class NomicEncoder:
 
     def hidden(self, b: Batch) -> torch.Tensor:
         """Final-layer hidden states [T, 768] (bf16) for a packed batch."""
-        if self.split_parts > 1 and self.schedule == "fused" and b.B >= 2 * self.split_parts:
-            return self._hidden_split(b, self.split_parts)
         if self.schedule == "folded":
             return self._hidden_folded(b)
         if self.schedule == "split":
             return self._hidden_unfused(b)
         if self.schedule != "fused":
             raise ValueError(f"unknown encoder schedule {self.schedule!r}")
-        return self._hidden_fused(b)
+        split = self.split_parts > 1 and b.B >= 2 * self.split_parts
+        return self._hidden_fused(b, self.split_parts if split else 1)
 
-    def _res_ln(self, A, W, M, x, g, beta):
-        """x[:M] = LN(A W^T + x) * g + beta in place (row-complete MFMA kernel, gemm_rln.hip)."""
-        N_, K = W.shape
-        _chk(self.L.nomic_gemm_res_ln(A.data_ptr(), A.stride(0), W.data_ptr(), W.stride(0), M, N_, K, x.data_ptr(),
-                                      x.stride(0), g.data_ptr(), beta.data_ptr(), self.cfg.eps, x.data_ptr(),
-                                      x.stride(0), _stream()), "gemm_res_ln")
-
-    def _hidden_fused(self, b: Batch) -> torch.Tensor:
-        """The shipped schedule: 5 kernels per layer, every one hand-written for gfx950 --
-        QKV+RoPE GEMM, varlen attention, o-proj+residual+LN, up|gate+SwiGLU GEMM, down+residual+LN."""
-        cfg, L, w = self.cfg, self.L, self.w
-        assert b.max_len <= self.rope.shape[0]
-        self._ensure(b.T_pad)
-        s = _stream()
+    def _layer_fused(self, lw, b: Batch, x, attn, qkv, ffn, s):
+        """One layer of the shipped schedule, 5 kernels, every one hand-written for gfx950: QKV+RoPE
+        GEMM, varlen attention, o-proj+residual+LN, up|gate+SwiGLU GEMM, down+residual+LN."""
         T = b.T
-        x, attn, qkv, ffn = self.x, self.attn, self.qkv, self.ffn
-        _chk(L.nomic_embed_ln(b.ids.data_ptr(), T, w.tok.data_ptr(), w.type_row.data_ptr(), w.emb_g.data_ptr(),
-                              w.emb_b.data_ptr(), cfg.eps, x.data_ptr(), s), "embed_ln")
-        scale = 1.0 / math.sqrt(cfg.head_dim)
-        for lw in w.layers:
-            self._gemm(EPI_ROPE, x, lw["wqkv"], T, qkv, pos=b.pos)
-            _chk(L.nomic_attention(qkv.data_ptr(), attn.data_ptr(), b.cu.data_ptr(), b.qblocks.data_ptr(), b.nqb,
-                                   cfg.heads, scale, s), "attention")
-            self._res_ln(attn, lw["wo"], T, x, lw["ln1_g"], lw["ln1_b"])
-            self._gemm(EPI_SWIGLU, x, lw["wupgate"], T, ffn)
-            self._res_ln(ffn, lw["wdown"], T, x, lw["ln2_g"], lw["ln2_b"])
-        return x[:T]
+        self._gemm(EPI_ROPE, x, lw["wqkv"], T, qkv, s, pos=b.pos)
+        self._attention(b, qkv, attn, s)
+        self._res_ln(attn, lw["wo"], T, x, lw["ln1_g"], lw["ln1_b"], s)
+        self._gemm(EPI_SWIGLU, x, lw["wupgate"], T, ffn, s)
+        self._res_ln(ffn, lw["wdown"], T, x, lw["ln2_g"], lw["ln2_b"], s)
 
-    def _hidden_split(self, b: Batch, parts: int) -> torch.Tensor:
-        """The fused schedule over `parts` document groups on their own streams (NOMIC_SPLIT); every
-        group works on its own rows of the shared workspaces, so the hidden states land in rows [0, T)
+    def _hidden_fused(self, b: Batch, parts: int = 1) -> torch.Tensor:
+        """The shipped schedule.  One group: the whole batch on the current stream, no side stream and
+        no wait.  parts > 1 (NOMIC_SPLIT): `parts` document groups on their own streams; every group
+        works on its own rows of the shared workspaces, so the hidden states land in rows [0, T)
         exactly as the one-stream forward leaves them."""
-        cfg, L, w = self.cfg, self.L, self.w
-        assert b.max_len <= self.rope.shape[0]
-        self._ensure(b.T_pad)
-        subs = b.split(parts)
-        if self._split_streams is None or len(self._split_streams) < len(subs):
-            self._split_streams = [torch.cuda.Stream() for _ in subs]
-        cur = torch.cuda.current_stream()
-        streams = self._split_streams[: len(subs)]
-        for st in streams:
-            st.wait_stream(cur)
-        scale = 1.0 / math.sqrt(cfg.head_dim)
-        views = []
-        for (sb, r0), st in zip(subs, streams):
-            views.append((sb, st, self.x[r0:], self.attn[r0:], self.qkv[r0:], self.ffn[r0:]))
-        for sb, st, x, attn, qkv, ffn in views:
-            with torch.cuda.stream(st):
-                _chk(L.nomic_embed_ln(sb.ids.data_ptr(), sb.T, w.tok.data_ptr(), w.type_row.data_ptr(),
-                                      w.emb_g.data_ptr(), w.emb_b.data_ptr(), cfg.eps, x.data_ptr(), st.cuda_stream),
-                     "embed_ln")
-        for lw in w.layers:
-            for sb, st, x, attn, qkv, ffn in views:
-                with torch.cuda.stream(st):
-                    s_ = st.cuda_stream
-                    T = sb.T
-                    self._gemm(EPI_ROPE, x, lw["wqkv"], T, qkv, pos=sb.pos)
-                    _chk(L.nomic_attention(qkv.data_ptr(), attn.data_ptr(), sb.cu.data_ptr(), sb.qblocks.data_ptr(),
-                                           sb.nqb, cfg.heads, scale, s_), "attention")
-                    self._res_ln(attn, lw["wo"], T, x, lw["ln1_g"], lw["ln1_b"])
-                    self._gemm(EPI_SWIGLU, x, lw["wupgate"], T, ffn)
-                    self._res_ln(ffn, lw["wdown"], T, x, lw["ln2_g"], lw["ln2_b"])
+        s = self._begin(b)
+        streams = []
+        groups = [(b, self.x, self.attn, self.qkv, self.ffn, s)]
+        if parts > 1:
+            subs = b.split(parts)
+            if self._split_streams is None or len(self._split_streams) < len(subs):
+                self._split_streams = [torch.cuda.Stream() for _ in subs]
+            cur = torch.cuda.current_stream()
+            streams = self._split_streams[: len(subs)]
+            for st in streams:
+                st.wait_stream(cur)
+            groups = [(sb, self.x[r0:], self.attn[r0:], self.qkv[r0:], self.ffn[r0:], st.cuda_stream)
+                      for (sb, r0), st in zip(subs, streams)]
+        for sb, x, _, _, _, gs in groups:
+            self._embed_ln(sb, x, gs)
+        for lw in self.w.layers:
+            for g in groups:
+                self._layer_fused(lw, *g)
         for st in streams:
             cur.wait_stream(st)
         return self.x[: b.T]
@@ -511,60 +523,45 @@ class NomicEncoder:
         them into (mean, rstd) per row in its prologue and runs on raw h against LN-folded weights,
         and the next residual GEMM normalises its residual operand on the fly.  One LayerNorm pass
         per forward (the final one, for pooling) instead of two per layer."""
-        cfg, L, w = self.cfg, self.L, self.w
-        assert b.max_len <= self.rope.shape[0]
-        self._ensure(b.T_pad)
-        s = _stream()
+        s = self._begin(b)
         T = b.T
         x, h1, h2, attn, qkv, ffn = self.x, self.h, self.h2, self.attn, self.qkv, self.ffn
         p1, p2 = self.part1, self.part2
-        _chk(L.nomic_embed_ln(b.ids.data_ptr(), T, w.tok.data_ptr(), w.type_row.data_ptr(), w.emb_g.data_ptr(),
-                              w.emb_b.data_ptr(), cfg.eps, x.data_ptr(), s), "embed_ln")
-        scale = 1.0 / math.sqrt(cfg.head_dim)
+        self._embed_ln(b, x, s)
         prev = None
-        for lw in w.layers:
+        for lw in self.w.folded():
             if prev is None:
-                self._gemm(EPI_ROPE, x, lw["wqkv"], T, qkv, pos=b.pos)
+                self._gemm(EPI_ROPE, x, lw["wqkv"], T, qkv, s, pos=b.pos)
             else:
-                self._gemm_ln(EPI_ROPE_FOLD, h2, lw["wqkv_f"], T, qkv, pos=b.pos, pin=p2, c1=lw["qkv_c1"],
+                self._gemm_ln(EPI_ROPE_FOLD, h2, lw["wqkv_f"], T, qkv, s, pos=b.pos, pin=p2, c1=lw["qkv_c1"],
                               c2=lw["qkv_c2"])
-            _chk(L.nomic_attention(qkv.data_ptr(), attn.data_ptr(), b.cu.data_ptr(), b.qblocks.data_ptr(), b.nqb,
-                                   cfg.heads, scale, s), "attention")
+            self._attention(b, qkv, attn, s)
             if prev is None:
-                self._gemm_ln(EPI_RES_STATS, attn, lw["wo"], T, h1, res=x, part=p1)
+                self._gemm_ln(EPI_RES_STATS, attn, lw["wo"], T, h1, s, res=x, part=p1)
             else:
-                self._gemm_ln(EPI_RES_LN_STATS, attn, lw["wo"], T, h1, res=h2, pin=p2,
+                self._gemm_ln(EPI_RES_LN_STATS, attn, lw["wo"], T, h1, s, res=h2, pin=p2,
                               ln=(prev["ln2_g"], prev["ln2_b"]), part=p1)
-            self._gemm_ln(EPI_SWIGLU_FOLD, h1, lw["wupgate_f"], T, ffn, pin=p1, c1=lw["ug_c1"], c2=lw["ug_c2"])
-            self._gemm_ln(EPI_RES_LN_STATS, ffn, lw["wdown"], T, h2, res=h1, pin=p1, ln=(lw["ln1_g"], lw["ln1_b"]),
-                          part=p2)
+            self._gemm_ln(EPI_SWIGLU_FOLD, h1, lw["wupgate_f"], T, ffn, s, pin=p1, c1=lw["ug_c1"], c2=lw["ug_c2"])
+            self._gemm_ln(EPI_RES_LN_STATS, ffn, lw["wdown"], T, h2, s, res=h1, pin=p1,
+                          ln=(lw["ln1_g"], lw["ln1_b"]), part=p2)
             prev = lw
-        _chk(L.nomic_layernorm(h2.data_ptr(), T, prev["ln2_g"].data_ptr(), prev["ln2_b"].data_ptr(), cfg.eps,
-                               x.data_ptr(), s), "ln_final")
+        self._layernorm(h2, T, prev["ln2_g"], prev["ln2_b"], x, s, "ln_final")
         return x[:T]
 
     def _hidden_unfused(self, b: Batch) -> torch.Tensor:
         """Split schedule: the residual GEMM, then a LayerNorm kernel (NOMIC_SCHEDULE=split)."""
-        cfg, L, w = self.cfg, self.L, self.w
-        assert b.max_len <= self.rope.shape[0]
-        self._ensure(b.T_pad)
-        s = _stream()
+        s = self._begin(b)
         T = b.T
         x, h, attn, qkv, ffn = self.x, self.h, self.attn, self.qkv, self.ffn
-        _chk(L.nomic_embed_ln(b.ids.data_ptr(), T, w.tok.data_ptr(), w.type_row.data_ptr(), w.emb_g.data_ptr(),
-                              w.emb_b.data_ptr(), cfg.eps, x.data_ptr(), s), "embed_ln")
-        scale = 1.0 / math.sqrt(cfg.head_dim)
-        for lw in w.layers:
-            self._gemm(EPI_ROPE, x, lw["wqkv"], T, qkv, pos=b.pos)
-            _chk(L.nomic_attention(qkv.data_ptr(), attn.data_ptr(), b.cu.data_ptr(), b.qblocks.data_ptr(), b.nqb,
-                                   cfg.heads, scale, s), "attention")
-            self._gemm(EPI_RESIDUAL, attn, lw["wo"], T, h, res=x)
-            _chk(L.nomic_layernorm(h.data_ptr(), T, lw["ln1_g"].data_ptr(), lw["ln1_b"].data_ptr(), cfg.eps,
-                                   x.data_ptr(), s), "ln1")
-            self._gemm(EPI_SWIGLU, x, lw["wupgate"], T, ffn)
-            self._gemm(EPI_RESIDUAL, ffn, lw["wdown"], T, h, res=x)
-            _chk(L.nomic_layernorm(h.data_ptr(), T, lw["ln2_g"].data_ptr(), lw["ln2_b"].data_ptr(), cfg.eps,
-                                   x.data_ptr(), s), "ln2")
+        self._embed_ln(b, x, s)
+        for lw in self.w.layers:
+            self._gemm(EPI_ROPE, x, lw["wqkv"], T, qkv, s, pos=b.pos)
+            self._attention(b, qkv, attn, s)
+            self._gemm(EPI_RESIDUAL, attn, lw["wo"], T, h, s, res=x)
+            self._layernorm(h, T, lw["ln1_g"], lw["ln1_b"], x, s, "ln1")
+            self._gemm(EPI_SWIGLU, x, lw["wupgate"], T, ffn, s)
+            self._gemm(EPI_RESIDUAL, ffn, lw["wdown"], T, h, s, res=x)
+            self._layernorm(h, T, lw["ln2_g"], lw["ln2_b"], x, s, "ln2")
         return x[:T]
 
     def embed(self, b: Batch, normalize: bool = False, arena=None, slots: Optional[torch.Tensor] = None,

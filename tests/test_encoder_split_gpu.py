@@ -1,4 +1,4 @@
-"""NOMIC_SPLIT (NomicEncoder._hidden_split over Batch.split): the document groups on their own
+"""NOMIC_SPLIT (NomicEncoder._hidden_fused with parts > 1, over Batch.split): the document groups on their own
 streams against the one-stream forward and the fp32 reference."""
 import numpy as np
 import pytest

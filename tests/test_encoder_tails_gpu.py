@@ -231,3 +231,25 @@ def test_rln_rows_not_16_byte_aligned_run_the_8_byte_form(L, form):
     assert _rel(X[:M, :768].float(), ref) < 6e-3
     assert (X[:M, :768].float() - ref).abs().max().item() < 0.08
     assert torch.equal(X[M:], tail) and torch.equal(X[:, 768:], pad)
+
+
+@pytest.mark.parametrize("K", [32, 64, 96, 128])
+@pytest.mark.parametrize("M", [1, 129])
+def test_rln_ring_edges_of_the_k_loop(L, M, K):
+    """The shortest K walks of the ring loop k_gemm_rln shares with k_gemm384: 32 = one stage with
+    nothing in flight behind it, 64 = the prologue issues alone, 96 = the first wrap of the W ring,
+    128 = the first reuse of an A slot after a wrap; one row, and two tiles with a row tail.  Form 222
+    against fp32 with the bounds of test_gemm_residual_layernorm_row_complete (a shorter K only lowers
+    the error), form 242 the same bits, rows past M untouched."""
+    import torch
+    A, W, X0, g, b, ref = _rln_operands(M, K, 768)
+    got = {}
+    for v in (222, 242):
+        X = X0.clone()
+        assert _rln(L, v, A, W, K, M, X, X, g, b) == 0
+        assert torch.equal(X[M:], X0[M:]), "rows past M must not be written"
+        got[v] = X
+    rel, err = _rel(got[222][:M].float(), ref), (got[222][:M].float() - ref).abs().max().item()
+    print(f"rln ring edge M={M} K={K}: rel {rel:.3e} max abs {err:.3e}")
+    assert rel < 6e-3 and err < 0.08
+    assert torch.equal(got[242], got[222]), "form 242 must give the bits of form 222"

@@ -330,6 +330,29 @@ def test_encoder_matches_fp32_reference(schedule):
     assert _rel(got, ref) < 3e-2
 
 
+def test_folded_weights_and_workspaces_exist_only_after_a_folded_forward():
+    """The default schedule neither builds the LN-folded weight copies nor allocates the workspaces
+    only the "folded" schedule reads; the first folded forward makes them, the second reuses them."""
+    from libsplinter_amd.models.nomic import Batch, NomicConfig, NomicEncoder, NomicWeights, random_weights
+    cfg = NomicConfig(layers=2)
+    w = NomicWeights.from_numpy(cfg, random_weights(cfg, seed=3))
+    enc = NomicEncoder(w, max_tokens=256)
+    assert enc.schedule == "fused"
+    b = Batch([[1, 2, 3, 4, 5], list(range(7, 47))])
+    enc.embed(b)
+    folded_keys, folded_ws = ("wupgate_f", "wqkv_f"), ("h2", "part1", "part2")
+    assert not any(k in lw for lw in w.layers for k in folded_keys)
+    assert all(getattr(enc, n, None) is None for n in folded_ws)
+    enc.schedule = "folded"
+    enc.embed(b)
+    assert all("wupgate_f" in lw for lw in w.layers) and "wqkv_f" in w.layers[1]
+    assert all(getattr(enc, n).shape[0] >= b.T_pad for n in folded_ws + ("h",))
+    first = [lw[k] for lw in w.layers for k in folded_keys if k in lw] + [getattr(enc, n) for n in folded_ws]
+    enc.embed(b)
+    again = [lw[k] for lw in w.layers for k in folded_keys if k in lw] + [getattr(enc, n) for n in folded_ws]
+    assert len(first) == 3 + 3 and all(x is y for x, y in zip(first, again))
+
+
 def test_gguf_roundtrip_device_dequant(tmp_path):
     import torch
     from libsplinter_amd.models.gguf import GGUFFile
