@@ -217,8 +217,6 @@ def _declare_hip(L):
     _sig(L, "spl_arena_get", c_int, A, P, c_int, P, c_int, P, c_long, P, c_int, P, P)
     _sig(L, "spl_arena_set_seg", c_int, A, P, c_int, P, c_int, P, c_long, P, c_int, P, P, c_long, P)
     _sig(L, "spl_arena_get_seg", c_int, A, P, c_int, P, c_int, P, c_long, P, c_int, P, P, c_long, P)
-    _sig(L, "spl_arena_set_idx", c_int, A, P, c_int, P, c_int, P, P, P, c_long, P, c_int, P, P)
-    _sig(L, "spl_arena_get_idx", c_int, A, P, c_int, P, c_int, P, P, P, c_long, P, c_int, P, P)
     # routed exchange (route_kernels.hip, parallel/xroute.py)
     _sig(L, "spl_xr_pack", c_int, P, c_int, P, c_int, P, c_long, c_int, c_int, c_long, P, c_long, c_long, c_long,
          c_int, P, P, P, c_long, P, P, P)

@@ -256,289 +256,16 @@ __device__ __forceinline__ void coop_copy_dma(const uint4* __restrict__ ep, cons
 }
 
 // ------------------------------------------------ carried-retry rounds -----
-// The batched set / get kernels (K2 / K3 of SURVEY §2.10).  U ops per lane per round: U claims
-// (or lookups) in flight, then the round's value rows move through the cooperative copy.  An op
-// that meets a contended slot (EAGAIN) is NOT retried inline: it stays in its lane's slot and is
-// retried in the lane's next round while the lane's other slots take new ops, so a round of other
-// work is the natural backoff.  Attempts per op are bounded by 1 + max_retry; the round loop is
-// block-uniform (barriers).  Lane sequence: op c of a lane is first + (c / U) * stride + c % U.
-// WT: the value rows and slot metadata go out as write-through `sc1` 16-B stores and each wave
-// publishes its own ops after its vmcnt(0) drain -- recipe R1 of cdna_hip_programming.md
-// Guideline 16 -- so a round needs neither the workgroup barrier pair nor the XCD-serialised L2
-// write-back of a release (default; SPLINTER_ARENA_COOP=1: plain rows + one release per round).
-template <int U, int B, bool WT>
-__global__ __launch_bounds__(B) void k_set_carry(spl_arena_t aa, const char* keys, int kstride, const uint8_t* vals,
-                                                 int vstride, const uint32_t* lens, long n, int32_t* status,
-                                                 int max_retry, uint64_t* stats, Seg seg) {
-  __shared__ uint4 cp_p[B / 64][U * 64];
-  __shared__ uint2 cp_l[B / 64][U * 64];
-  const Arena a = to_dev(aa);
-  bool hybrid;
-  const bool scrub = scrub_flags(a, hybrid);
-  Stats st;
-  uint32_t muts = 0;
-  const long stride = (long)gridDim.x * blockDim.x * U;
-  const long first = (long)blockIdx.x * blockDim.x * U + (long)threadIdx.x * U;
-  long cursor = 0;
-  bool more = true;
-  Key k[U];
-  Claim c[U];
-  uint32_t len[U];
-  long op[U];
-  int tries[U];
-  uint64_t ms = maint_begin(a);  // maintenance seq, re-read after every round's drain (arena_dev.hpp)
-#pragma unroll
-  for (int j = 0; j < U; ++j) op[j] = -1;
-  for (;;) {
-#pragma unroll
-    for (int j = 0; j < U; ++j) {
-      while (op[j] < 0 && more) {  // refill: next live op of this lane's sequence
-        const long i = first + (cursor / U) * stride + (cursor % U);
-        ++cursor;
-        if (i >= n) { more = false; break; }
-        if (!seg.live(i)) {
-          if (status && !seg.idx) status[i] = kInval;
-          continue;
-        }
-        const long r = seg.row(i);
-        op[j] = r;
-        tries[j] = 0;
-        load_key(k[j], keys + r * (long)kstride, kstride);
-        len[j] = lens[r];
-      }
-    }
-    bool busy = false;
-#pragma unroll
-    for (int j = 0; j < U; ++j) busy |= op[j] >= 0;
-    if (!__syncthreads_or(busy)) break;
-#pragma unroll
-    for (int j = 0; j < U; ++j) {
-      c[j] = Claim{-1, false, kInval};
-      if (op[j] >= 0) {
-        ++st.attempts;
-        ++tries[j];
-        if (len[j] == 0 || len[j] > a.max_val || len[j] > (uint32_t)vstride) c[j].rc = kMsgSize;
-        else c[j] = claim_set(a, k[j], ms);
-      }
-    }
-    // value rows through the cooperative copy (wave-private table), metadata per lane
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-    for (int j = 0; j < U; ++j) {
-      const bool go = op[j] >= 0 && c[j].rc == kOk;
-      const uint64_t sp = go ? (uint64_t)(vals + op[j] * (long)vstride) : 0;
-      const uint64_t dp = go ? (uint64_t)a.value((size_t)c[j].idx) : 0;
-      cp_p[w][j * 64 + lane] = make_uint4((uint32_t)sp, (uint32_t)(sp >> 32), (uint32_t)dp, (uint32_t)(dp >> 32));
-      cp_l[w][j * 64 + lane] = make_uint2(go ? len[j] : 0u, go ? set_chunks(a, len[j], scrub, hybrid) : 0u);
-    }
-    __builtin_amdgcn_wave_barrier();
-    coop_copy<U * 64, WT ? 3 : 0>(cp_p[w], cp_l[w], lane, (int)((a.max_val + 255) >> 8), a.max_val);
-#pragma unroll
-    for (int j = 0; j < U; ++j)
-      if (op[j] >= 0 && c[j].rc == kOk) write_meta<WT ? 3 : 0>(a, c[j], len[j]);
-    {
-      u32x2c_t mw = ld8c(maint_addr(a));
-      vm_wait1(mw);  // = drain(): the round's stores and this load
-      ms = u64of(mw);
-    }
-    if constexpr (!WT) {
-      __syncthreads();
-      if (threadIdx.x == 0) release();
-      __syncthreads();
-    }
-#pragma unroll
-    for (int j = 0; j < U; ++j) {
-      if (op[j] < 0) continue;
-      const int32_t rc = c[j].rc;
-      if (rc == kAgain) {
-        ++st.again;
-        if (tries[j] <= max_retry) continue;  // carried into the next round
-      }
-      if (rc == kOk) {
-        finish_set(a, c[j]);
-        ++st.ok;
-        ++muts;
-        pulse_masks(a, c[j].wm, c[j].bl);
-        mark_dirty(a, (size_t)c[j].idx);
-      }
-      if (status) status[op[j]] = rc;
-      op[j] = -1;
-    }
-  }
-  flush_stats(a, st, stats, muts);
-}
+// Every batched set / get of the arena (K2 / K3 of SURVEY §2.10) is a loop of rounds over a lane's U
+// op slots (kv_round, below): U claims (or lookups) in flight, then the round's value rows move
+// through the cooperative copy.  An op that meets a contended slot (EAGAIN) is NOT retried inline: it
+// stays in its lane's slot and is retried in the lane's next round while the lane's other slots take
+// new ops, so a round of other work is the natural backoff.  Attempts per op are bounded by
+// 1 + max_retry.  Three kernels feed the round from their own row sources: k_kv_batch (one kind, one
+// batch: spl_arena_set / spl_arena_get and the per-stream fan-outs), k_kv_fused (a whole KV step's
+// segments in one grid) and k_kv_server (slices posted by client streams).
 
-// FAST: no workgroup acquire.  Every load of slot words and value bytes is an `sc1` load,
-// which bypasses the (possibly stale) L1 and is served by the XCD's L2.  That is enough because every
-// writer of these bytes (k_set_carry WT, the ring's set) stores them write-through (`sc1`) and drains
-// vmcnt before publishing, so no dirty copy lingers in the writer XCD's L2, and an `sc1` load on another
-// XCD then returns the written bytes -- the "sc1 stores + sc1 loads" hand-off of the MI355X guide
-// (measured, not an architectural guarantee; pinned by tests/test_arena_gpu.py
-// test_acquire_free_get_cross_xcd_hot_keys; SPLINTER_ARENA_COOP_GET=1 is the acquire fallback).
-// Ops that store with plain (write-back) stores must release before a reader may rely on this (see
-// the ring's serve()).  The key is re-checked in the same round trip as the closing (hash, epoch)
-// load instead of a separate one before the copy: a key change between the probe and the value
-// loads moves the epoch or, for an unset that rewinds it, clears the hash.
-template <int U, int B, bool FAST>
-__global__ __launch_bounds__(B) void k_get_carry(spl_arena_t aa, const char* keys, int kstride, uint8_t* out,
-                                                 int ostride, uint32_t* out_lens, long n, int32_t* status,
-                                                 int max_retry, uint64_t* stats, Seg seg) {
-  __shared__ uint4 cp_p[B / 64][U * 64];
-  __shared__ uint2 cp_l[B / 64][U * 64];
-  const Arena a = to_dev(aa);
-  Stats st;
-  const long stride = (long)gridDim.x * blockDim.x * U;
-  const long first = (long)blockIdx.x * blockDim.x * U + (long)threadIdx.x * U;
-  long cursor = 0;
-  bool more = true;
-  Key k[U];
-  long op[U], sidx[U];
-  uint64_t e1[U];
-  int32_t rc[U];
-  uint32_t len[U];
-  int tries[U];
-  uint64_t ms = maint_begin(a);  // maintenance seq, re-read after every round's copies
-#pragma unroll
-  for (int j = 0; j < U; ++j) op[j] = -1;
-  for (;;) {
-#pragma unroll
-    for (int j = 0; j < U; ++j) {
-      while (op[j] < 0 && more) {
-        const long i = first + (cursor / U) * stride + (cursor % U);
-        ++cursor;
-        if (i >= n) { more = false; break; }
-        if (!seg.live(i)) {
-          if (!seg.idx) {
-            if (out_lens) out_lens[i] = 0;
-            if (status) status[i] = kInval;
-          }
-          continue;
-        }
-        const long r = seg.row(i);
-        op[j] = r;
-        tries[j] = 0;
-        load_key(k[j], keys + r * (long)kstride, kstride);
-      }
-    }
-    bool busy = false;
-#pragma unroll
-    for (int j = 0; j < U; ++j) busy |= op[j] >= 0;
-    if (!__syncthreads_or(busy)) break;
-#pragma unroll
-    for (int j = 0; j < U; ++j) {
-      rc[j] = kInval;
-      if (op[j] >= 0) {
-        ++st.attempts;
-        ++tries[j];
-        len[j] = 0;
-        sidx[j] = locate_peek(a, k[j], &e1[j], &len[j], ms);
-        rc[j] = sidx[j] >= 0 ? kOk : sidx[j] == kMaintMiss ? kAgain : kNoEnt;
-      }
-    }
-    if constexpr (FAST) {
-#pragma unroll
-      for (int j = 0; j < U; ++j) {
-        if (op[j] < 0 || rc[j] != kOk) continue;
-        if ((e1[j] & 1) || len[j] > a.max_val) rc[j] = kAgain;
-        else if (out && len[j] > (uint32_t)ostride) rc[j] = kMsgSize;
-      }
-    } else {
-      drain();
-      __syncthreads();
-      if (threadIdx.x == 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      __syncthreads();
-#pragma unroll
-      for (int j = 0; j < U; ++j) {
-        if (op[j] < 0 || rc[j] != kOk) continue;
-        const uint8_t* s = a.slot((size_t)sidx[j]);
-        if ((e1[j] & 1) || len[j] > a.max_val) { rc[j] = kAgain; continue; }
-        KeyProbe<16> kp;
-        kp.issue(s, k[j]);
-        kp.wait();
-        if (out && len[j] > (uint32_t)ostride) { rc[j] = kMsgSize; continue; }
-        if (!kp.eq(k[j])) rc[j] = kAgain;
-      }
-    }
-    {
-      // value rows of this round's matched ops through the cooperative copy (see coop_copy)
-      const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-      for (int j = 0; j < U; ++j) {
-        const bool go = out && op[j] >= 0 && rc[j] == kOk;
-        const uint64_t sp = go ? (uint64_t)a.value((size_t)sidx[j]) : 0;
-        const uint64_t dp = go ? (uint64_t)(out + op[j] * (long)ostride) : 0;
-        const uint32_t n16 = (len[j] + 15) >> 4;
-        cp_p[w][j * 64 + lane] = make_uint4((uint32_t)sp, (uint32_t)(sp >> 32), (uint32_t)dp, (uint32_t)(dp >> 32));
-        cp_l[w][j * 64 + lane] = make_uint2(go ? n16 * 16 : 0u, go ? n16 : 0u);
-      }
-      __builtin_amdgcn_wave_barrier();
-      coop_copy<U * 64, 0, FAST>(cp_p[w], cp_l[w], lane, (int)((a.max_val + 255) >> 8), 0xFFFFFFFFu);
-    }
-    {
-      u32x2c_t mw = ld8c(maint_addr(a));
-      vm_wait1(mw);  // = drain()
-      ms = u64of(mw);
-    }
-    if constexpr (FAST) {
-      // closing round trip: (hash, epoch) and the key words of every op of the lane together
-      u32x4c_t he[U];
-      KeyProbe<16> kp[U];
-#pragma unroll
-      for (int j = 0; j < U; ++j) {
-        const bool live = op[j] >= 0 && rc[j] == kOk;
-        const uint8_t* s = a.slot(live ? (size_t)sidx[j] : 0);
-        he[j] = ld16c(s + kOffHash);
-        kp[j].issue(s, k[j]);
-      }
-#pragma unroll
-      for (int j = 0; j < U; ++j) {
-        vm_wait(he[j]);
-        kp[j].wait();
-      }
-#pragma unroll
-      for (int j = 0; j < U; ++j)
-        if (op[j] >= 0 && rc[j] == kOk && (hi64(he[j]) != e1[j] || lo64(he[j]) != k[j].hash || !kp[j].eq(k[j])))
-          rc[j] = kAgain;
-    } else {
-#pragma unroll
-      for (int j = 0; j < U; ++j) {
-        if (op[j] < 0 || rc[j] != kOk) continue;
-        u32x4c_t he = ld16c(a.slot((size_t)sidx[j]) + kOffHash);  // hash + epoch: one request
-        vm_wait(he);
-        if (hi64(he) != e1[j] || lo64(he) != k[j].hash) rc[j] = kAgain;
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < U; ++j) {
-      if (op[j] < 0) continue;
-      const int32_t r = rc[j];
-      if (r == kAgain) {
-        ++st.again;
-        if (tries[j] <= max_retry) continue;
-      }
-      if (r == kOk) ++st.ok;
-      else if (r == kNoEnt) ++st.miss;
-      if (out_lens) out_lens[op[j]] = r == kOk ? len[j] : 0;
-      if (status) status[op[j]] = r;
-      op[j] = -1;
-    }
-  }
-  flush_stats(a, st, stats, 0);
-}
-
-// ------------------------------------------------------- fused set + get -----
-// One grid for a whole KV step (spl_kvs_step / spl_kvs_step_xr in fused mode): the step's row
-// segments -- the client streams' slices of the set and the get batch, or a routed step's own rows
-// (through lidx) and every peer's request block -- are consumed by one launch instead of one
-// dispatch per slice.  With 32 + 32 client streams the per-slice dispatches are capped by the
-// hardware queues (about 2 set and 2 get dispatches resident at a time, profiles/r3_pmc_kv.md), and
-// the step is latency bound (79 % of set wave cycles wait on memory); here every CU holds waves of
-// both kinds at once.  The op space is the concatenation of the segments' LIVE rows (a request
-// block's count is read on the device); lane sequence as the carried-retry kernels (op c of a lane:
-// first + (c / U) * stride + c % U): a round's U slots may hold sets and gets side by side, their
-// probes / claims in flight together; the value rows of the two kinds go through two
-// cooperative-copy passes (sets: write-through rows into the arena, as k_set_carry WT; gets: sc1
-// reads of arena rows, as k_get_carry FAST), then sets publish and gets re-validate.
+// A round's rows come from segments: FSeg records in a table the round indexes by OpSlots::seg.
 constexpr int kFusedSegs = 32;  // segments per fused launch (sets + gets; a routed step: 2 x world)
 
 struct FSeg {
@@ -562,7 +289,7 @@ struct FSegs {
   int ks;
 };
 
-// A lane's U op slots in the fused / server round loops.  OI: segments may map outputs elsewhere
+// A lane's U op slots in the round loops.  OI: segments may map outputs elsewhere
 // (FSeg::oidx, the routed step's direct responses); without it the output row is the input row and
 // costs no register.
 template <int U, int KW, bool OI = false>
@@ -593,12 +320,60 @@ __device__ __forceinline__ void fill_slot(OpSlots<U, KW, OI>& o, int j, const FS
   o.len[j] = o.set[j] ? f.lens[o.row[j]] : 0u;
 }
 
+// KIND of kv_round: which kinds a lane's slots may hold.  A one-kind instantiation carries nothing of
+// the other kind (no table writes, copy pass, closing loads or registers) and takes no LDS table pair
+// for it (its caller passes nullptr); its segment table is ONE record, sg[0], and o.seg[j] only tells a
+// busy slot (0) from an empty one (-1), so the record can live in registers (k_kv_batch).
+constexpr int kKindSet = 1, kKindGet = 2, kKindBoth = 3;
+// COH of kv_round: the coherence form.
+//   kCohSc1 (default, and the only form of the fused and server grids): the value rows and slot metadata
+//     of a set go out as write-through `sc1` 16-B stores and each wave publishes its own ops after its
+//     vmcnt(0) drain -- recipe R1 of cdna_hip_programming.md Guideline 16 -- so a round needs neither a
+//     workgroup barrier pair nor the XCD-serialised L2 write-back of a release.  A get takes no acquire:
+//     every load of slot words and value bytes is an `sc1` load, which bypasses the (possibly stale) L1
+//     and is served by the XCD's L2.  That is enough because every writer of these bytes (this form's
+//     sets, the ring's set) stores them write-through and drains vmcnt before publishing, so no dirty
+//     copy lingers in the writer XCD's L2, and an `sc1` load on another XCD then returns the written
+//     bytes -- the "sc1 stores + sc1 loads" hand-off of the MI355X guide (measured, not an architectural
+//     guarantee; pinned by tests/test_arena_gpu.py test_acquire_free_get_cross_xcd_hot_keys).  Ops that
+//     store with plain (write-back) stores must release before a reader may rely on this (see the ring's
+//     serve()).  The key is re-checked in the same round trip as the closing (hash, epoch) load instead
+//     of a separate one before the copy: a key change between the probe and the value loads moves the
+//     epoch or, for an unset that rewinds it, clears the hash.
+//   kCohFence (SPLINTER_ARENA_COOP=1 / SPLINTER_ARENA_COOP_GET=1, the fallback of k_kv_batch): a set
+//     writes plain rows and metadata, then the workgroup meets, thread 0 releases once for the round, and
+//     it meets again before anything is published; a get drains, the workgroup meets, thread 0 takes one
+//     agent acquire, then the stored key is probed BEFORE the copy, the rows are read with plain loads,
+//     and the close re-checks (hash, epoch) alone.  THIS FORM CONTAINS WORKGROUP BARRIERS: only a round
+//     loop that every lane of the workgroup leaves together (a block-uniform exit vote) may instantiate
+//     it, never a wave-vote loop (kSchedWaves, the server's WV) -- that cannot be asserted here; what can
+//     is that it is a one-kind round.
+constexpr int kCohSc1 = 0, kCohFence = 1;
+
+template <int KIND>
+__device__ __forceinline__ const FSeg& seg_of(const FSeg* sg, int q) {
+  if constexpr (KIND == kKindBoth) return sg[q];
+  else return sg[0];
+}
+template <int KIND, int U, int KW, bool OI>
+__device__ __forceinline__ bool is_set(const OpSlots<U, KW, OI>& o, int j) {
+  if constexpr (KIND == kKindBoth) return o.set[j];
+  else return KIND == kKindSet;
+}
+template <int COH, int KW>
+__device__ __forceinline__ bool key_still(const KeyProbe<KW>& kp, const KeyT<KW>& k) {
+  if constexpr (COH == kCohSc1) return kp.eq(k);
+  else return true;  // kCohFence: probed before the copy
+}
+
 // One round over a lane's U slots: probes / claims of every occupied slot, the two cooperative row
 // copies (cp*0: set rows, cp*1: get rows; a wave-private LDS table each), set publication, get
 // re-validation, completion.  An op that met EAGAIN stays in its slot for the next round while
-// tries <= max_retry.  Called by every lane of the wave (the row copies are wave-cooperative).
+// tries <= max_retry.  Called by every lane of the wave (the row copies are wave-cooperative); kCohFence:
+// by every lane of the workgroup.
 // ms: the arena's maintenance seq as read (and waited for) before this round's probes; re-read in
-// the round's closing round trip for the next round (arena_dev.hpp, online maintenance).
+// the round's closing round trip for the next round (arena_dev.hpp, online maintenance).  In a set-only
+// round that re-read is also the round's drain (one wait, not two).
 // flags: kKvSkipLen (an update that keeps its length leaves val_len alone).  (Measured and removed in
 // round 6: a get's home-slot value row requested by LDS-DMA beside its probe, 4.45-4.47 vs 4.84-4.88 G
 // ops/s KV-only: the extra requests cost more than the row copy's L2 hit saves, profiles/r6/README.md.)
@@ -613,11 +388,17 @@ constexpr int kKvStageKB = 6;  // LDS-DMA stage per wave (KB): 24 rows in flight
 // one (a read-modify-write below the HBM3E ECC granule): KV-only 5.35-5.47 vs 5.15-5.24 G ops/s, mixed
 // step 12.06-12.10 vs 12.30 ms (profiles/r6/README.md)
 constexpr int kKvPadOut = 8;
-template <int U, int KW, bool OI = false>
+// flags == 0 (k_kv_batch): a set always writes val_len, a get writes exactly ceil(len / 16) chunks and
+// nothing past them, and no LDS stage is needed.
+template <int U, int KW, bool OI = false, int KIND = kKindBoth, int COH = kCohSc1>
 __device__ __forceinline__ void kv_round(const Arena& a, const FSeg* sg, OpSlots<U, KW, OI>& o, bool scrub, bool hybrid,
                                          int max_retry, Stats& st, uint32_t& muts, uint4* cpp0, uint2* cpl0,
                                          uint4* cpp1, uint2* cpl1, int lane, int flags, uint64_t& ms,
                                          uint4* stage = nullptr) {
+  static_assert(KIND == kKindSet || KIND == kKindGet || KIND == kKindBoth, "kinds of a round");
+  static_assert(COH == kCohSc1 || (COH == kCohFence && KIND != kKindBoth), "the fence form is a one-kind round");
+  constexpr bool kSets = (KIND & kKindSet) != 0, kGets = (KIND & kKindGet) != 0;
+  constexpr int kMO = COH == kCohSc1 ? 3 : 0;  // store flavour of a set's rows and metadata (st16<MO>)
   const bool skip_len = flags & kKvSkipLen;
   Claim c[U];
   long sidx[U];
@@ -631,18 +412,22 @@ __device__ __forceinline__ void kv_round(const Arena& a, const FSeg* sg, OpSlots
     if (o.seg[j] < 0) continue;
     ++st.attempts;
     ++o.tries[j];
-    const int vs = sg[o.seg[j]].vstride;
-    if (o.set[j]) {
-      if (o.len[j] == 0 || o.len[j] > a.max_val || o.len[j] > (uint32_t)vs) c[j].rc = kMsgSize;
-      else c[j] = claim_set(a, o.k[j], ms);
-      rc[j] = c[j].rc;
+    const int vs = seg_of<KIND>(sg, o.seg[j]).vstride;
+    if (is_set<KIND>(o, j)) {
+      if constexpr (kSets) {
+        if (o.len[j] == 0 || o.len[j] > a.max_val || o.len[j] > (uint32_t)vs) c[j].rc = kMsgSize;
+        else c[j] = claim_set(a, o.k[j], ms);
+        rc[j] = c[j].rc;
+      }
     } else {
-      uint32_t L = 0;
-      sidx[j] = locate_peek(a, o.k[j], &e1[j], &L, ms);
-      o.len[j] = L;
-      rc[j] = sidx[j] >= 0 ? kOk : sidx[j] == kMaintMiss ? kAgain : kNoEnt;
-      if (rc[j] == kOk && ((e1[j] & 1) || L > a.max_val)) rc[j] = kAgain;
-      else if (rc[j] == kOk && sg[o.seg[j]].vals && L > (uint32_t)vs) rc[j] = kMsgSize;
+      if constexpr (kGets) {
+        uint32_t L = 0;
+        sidx[j] = locate_peek(a, o.k[j], &e1[j], &L, ms);
+        o.len[j] = L;
+        rc[j] = sidx[j] >= 0 ? kOk : sidx[j] == kMaintMiss ? kAgain : kNoEnt;
+        if (rc[j] == kOk && ((e1[j] & 1) || L > a.max_val)) rc[j] = kAgain;
+        else if (rc[j] == kOk && seg_of<KIND>(sg, o.seg[j]).vals && L > (uint32_t)vs) rc[j] = kMsgSize;
+      }
     }
   }
   // an update that keeps its length leaves val_len alone (SPL_KVS_SKIP_LEN, default 1: KV-only 4.94-4.96
@@ -650,76 +435,113 @@ __device__ __forceinline__ void kv_round(const Arena& a, const FSeg* sg, OpSlots
   // makes the slot's val_len stable, and a 4-B write is a partial-line write (read-modify-write
   // below the 64-B ECC granule of HBM3E); the loads are issued here and consumed after the row copies
   uint32_t oldlen[U];
+  if constexpr (kSets) {
 #pragma unroll
-  for (int j = 0; j < U; ++j) {
-    oldlen[j] = 0xFFFFFFFFu;
-    if (skip_len && o.seg[j] >= 0 && o.set[j] && rc[j] == kOk && !c[j].fresh)
-      oldlen[j] = ald32(a.slot((size_t)c[j].idx) + kOffValLen);
+    for (int j = 0; j < U; ++j) {
+      oldlen[j] = 0xFFFFFFFFu;
+      if (skip_len && o.seg[j] >= 0 && is_set<KIND>(o, j) && rc[j] == kOk && !c[j].fresh)
+        oldlen[j] = ald32(a.slot((size_t)c[j].idx) + kOffValLen);
+    }
+  }
+  if constexpr (kGets && COH == kCohFence) {
+    drain();
+    __syncthreads();
+    if (threadIdx.x == 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < U; ++j) {
+      if (o.seg[j] < 0 || rc[j] != kOk) continue;
+      KeyProbe<KW> kp;
+      kp.issue(a.slot((size_t)sidx[j]), o.k[j]);
+      kp.wait();
+      if (!kp.eq(o.k[j])) rc[j] = kAgain;
+    }
   }
   // value rows: table 0 = sets (client row -> arena, write-through), table 1 = gets (arena -> client)
 #pragma unroll
   for (int j = 0; j < U; ++j) {
-    const FSeg* f = o.seg[j] >= 0 ? &sg[o.seg[j]] : nullptr;
-    const bool gs = f && o.set[j] && rc[j] == kOk;
-    const bool gg = f && f->vals && !o.set[j] && rc[j] == kOk;
-    const uint64_t ss = gs ? (uint64_t)(f->vals + o.row[j] * (long)f->vstride) : 0;
-    const uint64_t sd = gs ? (uint64_t)a.value((size_t)c[j].idx) : 0;
-    cpp0[j * 64 + lane] = make_uint4((uint32_t)ss, (uint32_t)(ss >> 32), (uint32_t)sd, (uint32_t)(sd >> 32));
-    cpl0[j * 64 + lane] = make_uint2(gs ? o.len[j] : 0u, gs ? set_chunks(a, o.len[j], scrub, hybrid) : 0u);
-    const uint64_t gsrc = gg ? (uint64_t)a.value((size_t)sidx[j]) : 0;
-    const uint64_t gdst = gg ? (uint64_t)(f->vals + out_row(o, j) * (long)f->vstride) : 0;
-    const uint32_t n16 = (o.len[j] + 15) >> 4;
-    cpp1[j * 64 + lane] = make_uint4((uint32_t)gsrc, (uint32_t)(gsrc >> 32), (uint32_t)gdst, (uint32_t)(gdst >> 32));
-    // kKvPadOut: the output row is written to the next 64-B boundary (zeros past the value, inside the
-    // row's stride), so its last line is a whole-line write instead of a partial one
-    uint32_t wend = n16;
-    if ((flags & kKvPadOut) && gg) {
-      const uint32_t pad = (n16 + 3u) & ~3u, cap = (uint32_t)f->vstride >> 4;
-      wend = pad < cap ? pad : (cap > n16 ? cap : n16);
+    const FSeg* f = o.seg[j] >= 0 ? &seg_of<KIND>(sg, o.seg[j]) : nullptr;
+    const bool gs = f && is_set<KIND>(o, j) && rc[j] == kOk;
+    const bool gg = f && f->vals && !is_set<KIND>(o, j) && rc[j] == kOk;
+    if constexpr (kSets) {
+      const uint64_t ss = gs ? (uint64_t)(f->vals + o.row[j] * (long)f->vstride) : 0;
+      const uint64_t sd = gs ? (uint64_t)a.value((size_t)c[j].idx) : 0;
+      cpp0[j * 64 + lane] = make_uint4((uint32_t)ss, (uint32_t)(ss >> 32), (uint32_t)sd, (uint32_t)(sd >> 32));
+      cpl0[j * 64 + lane] = make_uint2(gs ? o.len[j] : 0u, gs ? set_chunks(a, o.len[j], scrub, hybrid) : 0u);
     }
-    cpl1[j * 64 + lane] = make_uint2(gg ? n16 * 16 : 0u, gg ? wend : 0u);
+    if constexpr (kGets) {
+      const uint64_t gsrc = gg ? (uint64_t)a.value((size_t)sidx[j]) : 0;
+      const uint64_t gdst = gg ? (uint64_t)(f->vals + out_row(o, j) * (long)f->vstride) : 0;
+      const uint32_t n16 = (o.len[j] + 15) >> 4;
+      cpp1[j * 64 + lane] = make_uint4((uint32_t)gsrc, (uint32_t)(gsrc >> 32), (uint32_t)gdst, (uint32_t)(gdst >> 32));
+      // kKvPadOut: the output row is written to the next 64-B boundary (zeros past the value, inside the
+      // row's stride), so its last line is a whole-line write instead of a partial one
+      uint32_t wend = n16;
+      if ((flags & kKvPadOut) && gg) {
+        const uint32_t pad = (n16 + 3u) & ~3u, cap = (uint32_t)f->vstride >> 4;
+        wend = pad < cap ? pad : (cap > n16 ? cap : n16);
+      }
+      cpl1[j * 64 + lane] = make_uint2(gg ? n16 * 16 : 0u, gg ? wend : 0u);
+    }
   }
   __builtin_amdgcn_wave_barrier();
 #ifndef SPL_KV_COPY_UNR
 #define SPL_KV_COPY_UNR 4
 #endif
 #ifndef SPL_KV_DIAG_NO_COPY
-  if ((flags & kKvCopyDma) && stage && a.max_val <= 256) {
-    coop_copy_dma<U * 64, 3, false, kKvStageKB>(cpp0, cpl0, lane, a.max_val, stage);
-    coop_copy_dma<U * 64, 0, true, kKvStageKB>(cpp1, cpl1, lane, 0xFFFFFFFFu, stage);
+  if (COH == kCohSc1 && (flags & kKvCopyDma) && stage && a.max_val <= 256) {
+    if constexpr (kSets) coop_copy_dma<U * 64, 3, false, kKvStageKB>(cpp0, cpl0, lane, a.max_val, stage);
+    if constexpr (kGets) coop_copy_dma<U * 64, 0, true, kKvStageKB>(cpp1, cpl1, lane, 0xFFFFFFFFu, stage);
   } else {
-    coop_copy<U * 64, 3, false, SPL_KV_COPY_UNR>(cpp0, cpl0, lane, (int)((a.max_val + 255) >> 8), a.max_val);
-    coop_copy<U * 64, 0, true, SPL_KV_COPY_UNR>(cpp1, cpl1, lane, (int)((a.max_val + 255) >> 8), 0xFFFFFFFFu);
+    if constexpr (kSets)
+      coop_copy<U * 64, kMO, false, SPL_KV_COPY_UNR>(cpp0, cpl0, lane, (int)((a.max_val + 255) >> 8), a.max_val);
+    if constexpr (kGets)
+      coop_copy<U * 64, 0, COH == kCohSc1, SPL_KV_COPY_UNR>(cpp1, cpl1, lane, (int)((a.max_val + 255) >> 8),
+                                                             0xFFFFFFFFu);
   }
 #endif
+  if constexpr (kSets) {
 #pragma unroll
-  for (int j = 0; j < U; ++j)
-    if (o.seg[j] >= 0 && o.set[j] && rc[j] == kOk && oldlen[j] != o.len[j]) write_meta<3>(a, c[j], o.len[j]);
-  drain();
+    for (int j = 0; j < U; ++j)
+      if (o.seg[j] >= 0 && is_set<KIND>(o, j) && rc[j] == kOk && oldlen[j] != o.len[j])
+        write_meta<kMO>(a, c[j], o.len[j]);
+  }
+  if constexpr (kGets) drain();
   // gets: closing round trip, (hash, epoch) and the key words together
   {
     u32x4c_t he[U];
     KeyProbe<KW> kp[U];
+    if constexpr (kGets) {
 #pragma unroll
-    for (int j = 0; j < U; ++j) {
-      const bool live = o.seg[j] >= 0 && !o.set[j] && rc[j] == kOk;
-      const uint8_t* s = a.slot(live ? (size_t)sidx[j] : 0);
-      he[j] = ld16c(s + kOffHash);
-      kp[j].issue(s, o.k[j]);
+      for (int j = 0; j < U; ++j) {
+        const bool live = o.seg[j] >= 0 && !is_set<KIND>(o, j) && rc[j] == kOk;
+        const uint8_t* s = a.slot(live ? (size_t)sidx[j] : 0);
+        he[j] = ld16c(s + kOffHash);
+        if constexpr (COH == kCohSc1) kp[j].issue(s, o.k[j]);
+      }
     }
     u32x2c_t mw = ld8c(maint_addr(a));  // the next round's maintenance seq, in the same round trip
+    if constexpr (kGets) {
 #pragma unroll
-    for (int j = 0; j < U; ++j) {
-      vm_wait(he[j]);
-      kp[j].wait();
+      for (int j = 0; j < U; ++j) {
+        vm_wait(he[j]);
+        if constexpr (COH == kCohSc1) kp[j].wait();
+      }
     }
-    vm_wait1(mw);
+    vm_wait1(mw);  // (a set-only round: = drain(), the round's stores and this load)
     ms = u64of(mw);
+    if constexpr (kGets) {
 #pragma unroll
-    for (int j = 0; j < U; ++j)
-      if (o.seg[j] >= 0 && !o.set[j] && rc[j] == kOk &&
-          (hi64(he[j]) != e1[j] || lo64(he[j]) != o.k[j].hash || !kp[j].eq(o.k[j])))
-        rc[j] = kAgain;
+      for (int j = 0; j < U; ++j)
+        if (o.seg[j] >= 0 && !is_set<KIND>(o, j) && rc[j] == kOk &&
+            (hi64(he[j]) != e1[j] || lo64(he[j]) != o.k[j].hash || !key_still<COH>(kp[j], o.k[j])))
+          rc[j] = kAgain;
+    }
+  }
+  if constexpr (kSets && COH == kCohFence) {
+    __syncthreads();
+    if (threadIdx.x == 0) release();
+    __syncthreads();
   }
 #pragma unroll
   for (int j = 0; j < U; ++j) {
@@ -729,25 +551,140 @@ __device__ __forceinline__ void kv_round(const Arena& a, const FSeg* sg, OpSlots
       ++st.again;
       if (o.tries[j] <= max_retry) continue;  // carried into the next round
     }
-    const FSeg& f = sg[o.seg[j]];
-    if (o.set[j]) {
-      if (r == kOk) {
-        finish_set(a, c[j]);
-        ++st.ok;
-        ++muts;
-        pulse_masks(a, c[j].wm, c[j].bl);
-        mark_dirty(a, (size_t)c[j].idx);
+    const FSeg& f = seg_of<KIND>(sg, o.seg[j]);
+    if (is_set<KIND>(o, j)) {
+      if constexpr (kSets) {
+        if (r == kOk) {
+          finish_set(a, c[j]);
+          ++st.ok;
+          ++muts;
+          pulse_masks(a, c[j].wm, c[j].bl);
+          mark_dirty(a, (size_t)c[j].idx);
+        }
       }
     } else {
-      if (r == kOk) ++st.ok;
-      else if (r == kNoEnt) ++st.miss;
-      if (f.lens) f.lens[out_row(o, j)] = r == kOk ? o.len[j] : 0;
+      if constexpr (kGets) {
+        if (r == kOk) ++st.ok;
+        else if (r == kNoEnt) ++st.miss;
+        if (f.lens) f.lens[out_row(o, j)] = r == kOk ? o.len[j] : 0;
+      }
     }
     if (f.status) f.status[out_row(o, j)] = r;
     o.seg[j] = -1;
   }
 }
 
+// ---- row sources of the round loops ----
+// Fixed lane streams: lane i of the grid takes rows i * U .. i * U + U - 1, then the same U rows one
+// grid stride on: op c of a lane is row first + (c / U) * stride + c % U, with
+//   stride = gridDim.x * blockDim.x * U,  first = blockIdx.x * blockDim.x * U + threadIdx.x * U.
+// (A function of values and no more: a stream object, a function that advances the cursor through a
+// reference, even functions for `first` and `stride`, changed the fused kernels' instructions,
+// profiles/kv_round/README.md.)
+template <int U>
+__device__ __forceinline__ long lane_row(long first, long stride, long c) {
+  return first + (c / U) * stride + (c % U);
+}
+
+// A lane's walk over a chunk of rows its workgroup (B lanes) has claimed: it starts at the chunk's row
+// threadIdx.x * U and takes U consecutive rows per B * U, so a round's U slots of a wave cover 64 * U
+// consecutive rows.  The step past `row` (which the caller has put into a slot) is shared as text, for the
+// same reason; `row` is int32_t where the launcher has checked rows < 2^31, and a register less.
+#define KV_CHUNK_STEP(row, part)                 \
+  if (++part == U) {                             \
+    part = 0;                                    \
+    row += (decltype(row))B * U - (U - 1);       \
+  } else {                                       \
+    ++row;                                       \
+  }
+
+// `busy`: some slot of the lane holds an op.  Text as well (a function over the slots, taken by reference,
+// by value or through a pointer to o.seg, changed the kernels).
+#define KV_ANY_BUSY(busy, o) \
+  bool busy = false;          \
+  _Pragma("unroll") for (int j = 0; j < U; ++j) busy |= (o).seg[j] >= 0;
+
+// A round loop's exit vote: WAVE, the wave's lanes alone (its waves never wait for each other), else the
+// workgroup's (a barrier)
+template <bool WAVE>
+__device__ __forceinline__ bool vote(bool p) {
+  if constexpr (WAVE) return __any(p);
+  else return __syncthreads_or(p);
+}
+
+// ------------------------------------------------------------- one batch -----
+// A batch of one kind (spl_arena_set / spl_arena_get and their _seg forms, the per-stream fan-outs of
+// mode 0): the Seg row source -- fixed lane streams over the launch's rows, dead rows skipped -- and the
+// shared round over a one-record segment table made of the kernel arguments.  No kv_round flags: a set
+// always writes val_len, a get writes exactly ceil(len / 16) chunks of its output row.  The round loop is
+// block-uniform (its exit vote is a workgroup barrier), so either coherence form may be used: kCohSc1 by
+// default, kCohFence under SPLINTER_ARENA_COOP=1 (sets) / SPLINTER_ARENA_COOP_GET=1 (gets).  Keys are
+// held in 16 words at every kstride.
+// vals / lens: a set's input rows and lengths, a get's output rows (null: statuses and lengths only)
+// and lengths (nullable).
+template <int U, int B, int KIND, int COH>
+__global__ __launch_bounds__(B) void k_kv_batch(spl_arena_t aa, const char* keys, int kstride, uint8_t* vals,
+                                                int vstride, uint32_t* lens, long n, int32_t* status, int max_retry,
+                                                uint64_t* stats, Seg seg) {
+  static_assert(KIND == kKindSet || KIND == kKindGet, "one kind per batch");
+  constexpr bool kSet = KIND == kKindSet;
+  __shared__ uint4 cp_p[B / 64][U * 64];  // the one table pair of this kind
+  __shared__ uint2 cp_l[B / 64][U * 64];
+  const Arena a = to_dev(aa);
+  bool hybrid = false, scrub = false;
+  if constexpr (kSet) scrub = scrub_flags(a, hybrid);
+  const FSeg f{keys, vals, lens, status, seg.idx, nullptr, n, vstride, kSet ? 1 : 0, nullptr};
+  Stats st;
+  uint32_t muts = 0;
+  const long stride = (long)gridDim.x * blockDim.x * U;
+  const long first = (long)blockIdx.x * blockDim.x * U + (long)threadIdx.x * U;
+  long cursor = 0;
+  bool more = true;
+  OpSlots<U, 16> o;
+#pragma unroll
+  for (int j = 0; j < U; ++j) o.seg[j] = -1;
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  uint64_t ms = maint_begin(a);  // maintenance seq, re-read in every round's closing round trip
+  for (;;) {
+#pragma unroll
+    for (int j = 0; j < U; ++j) {
+      while (o.seg[j] < 0 && more) {  // refill: next live row of this lane's stream
+        const long i = lane_row<U>(first, stride, cursor++);
+        if (i >= n) {
+          more = false;
+          break;
+        }
+        if (!seg.live(i)) {
+          if (!seg.idx) {  // (in-place rows: a dead row is no client op, nothing is written)
+            if (!kSet && lens) lens[i] = 0;
+            if (status) status[i] = kInval;
+          }
+          continue;
+        }
+        fill_slot(o, j, f, 0, i, kstride);
+      }
+    }
+    KV_ANY_BUSY(busy, o)
+    if (!vote<false>(busy)) break;
+    kv_round<U, 16, false, KIND, COH>(a, &f, o, scrub, hybrid, max_retry, st, muts, kSet ? cp_p[w] : nullptr,
+                                      kSet ? cp_l[w] : nullptr, kSet ? nullptr : cp_p[w], kSet ? nullptr : cp_l[w],
+                                      lane, 0, ms);
+  }
+  flush_stats(a, st, stats, muts);
+}
+
+// ------------------------------------------------------- fused set + get -----
+// One grid for a whole KV step (spl_kvs_step / spl_kvs_step_xr in fused mode): the step's row
+// segments -- the client streams' slices of the set and the get batch, or a routed step's own rows
+// (through lidx) and every peer's request block -- are consumed by one launch instead of one
+// dispatch per slice.  With 32 + 32 client streams the per-slice dispatches are capped by the
+// hardware queues (about 2 set and 2 get dispatches resident at a time, profiles/r3_pmc_kv.md), and
+// the step is latency bound (79 % of set wave cycles wait on memory); here every CU holds waves of
+// both kinds at once.  The op space is the concatenation of the segments' LIVE rows (a request
+// block's count is read on the device): a round's U slots may hold sets and gets side by side, their
+// probes / claims in flight together; the value rows of the two kinds go through two
+// cooperative-copy passes, then sets publish and gets re-validate (kv_round, kKindBoth, kCohSc1).
+//
 // SCHED, how a workgroup's lanes get their rows and when its round loop ends:
 //   0 kSchedBarrier: fixed lane streams (lane i of the grid: rows i, i + stride, ...), the loop's exit
 //     test a workgroup barrier each round (the round-5 form);
@@ -842,19 +779,14 @@ __global__ __launch_bounds__(B) __attribute__((amdgpu_waves_per_eu(OCC))) void k
           int q = 0;
           while (q + 1 < nseg && sstart[q + 1] <= row) ++q;
           fill_slot(o, j, sg[q], q, row - sstart[q], ks);
-          if (++part == U) {
-            part = 0;
-            row += B * U - (U - 1);
-          } else {
-            ++row;
-          }
+          KV_CHUNK_STEP(row, part)
         }
       }
     } else {
 #pragma unroll
       for (int j = 0; j < U; ++j) {
         if (o.seg[j] < 0 && more) {
-          const long i = first + (cursor / U) * stride + (cursor % U);
+          const long i = lane_row<U>(first, stride, cursor);
           ++cursor;
           if (i >= n) {
             more = false;
@@ -866,10 +798,8 @@ __global__ __launch_bounds__(B) __attribute__((amdgpu_waves_per_eu(OCC))) void k
         }
       }
     }
-    bool busy = false;
-#pragma unroll
-    for (int j = 0; j < U; ++j) busy |= o.seg[j] >= 0;
-    if (!(SCHED == kSchedWaves ? __any(busy) : __syncthreads_or(busy))) {
+    KV_ANY_BUSY(busy, o)
+    if (!vote<SCHED == kSchedWaves>(busy)) {
       if (SCHED == kSchedChunks && more) continue;  // (uniform: every lane's chunk rows are used up) the next claim
       break;
     }
@@ -1056,10 +986,8 @@ __global__ __launch_bounds__(B) __attribute__((amdgpu_waves_per_eu(OCC))) void k
       }
       break;
     }
-    bool carried = false;
-#pragma unroll
-    for (int j = 0; j < U; ++j) carried |= o.seg[j] >= 0;
-    carried = __syncthreads_or(carried);
+    KV_ANY_BUSY(held, o)
+    const bool carried = vote<false>(held);
     if (state == 0) {
       // nothing claimable yet: carried ops still progress
       if (carried)
@@ -1071,38 +999,28 @@ __global__ __launch_bounds__(B) __attribute__((amdgpu_waves_per_eu(OCC))) void k
     }
     const int q = sh_kind;
     const long end = sh_e;
-    long row = sh_b + (long)threadIdx.x * U;  // the lane's next row: U consecutive rows per B * U
+    long row = sh_b + (long)threadIdx.x * U;  // the lane's next row of the chunk
     int part = 0;
     for (;;) {
 #pragma unroll
       for (int j = 0; j < U; ++j) {
         if (o.seg[j] < 0 && row < end) {
           fill_slot(o, j, sg[q], q, row, ks);
-          if (++part == U) {
-            part = 0;
-            row += (long)B * U - (U - 1);
-          } else {
-            ++row;
-          }
+          KV_CHUNK_STEP(row, part)
         }
       }
-      bool busy = false;
-#pragma unroll
-      for (int j = 0; j < U; ++j) busy |= o.seg[j] >= 0;
       // once no lane has rows of this chunk left the group claims the next one; the ops still in
       // slots (the chunk's last fills, carried retries) ride along into its rounds
-      const bool more = row < end;
-      if (!(WV ? __any(more && busy) : __syncthreads_or(more && busy))) break;
+      KV_ANY_BUSY(busy, o)
+      if (!vote<WV>(row < end && busy)) break;
       kv_round<U, KW>(a, sg, o, scrub, hybrid, max_retry, st, muts, cp_p[0][w], cp_l[0][w], cp_p[1][w], cp_l[1][w],
                       lane, skip_len, ms, cp_stage[w]);
     }
   }
   // the last chunk's ops and any carried retries
   for (;;) {
-    bool busy = false;
-#pragma unroll
-    for (int j = 0; j < U; ++j) busy |= o.seg[j] >= 0;
-    if (!(WV ? __any(busy) : __syncthreads_or(busy))) break;
+    KV_ANY_BUSY(busy, o)
+    if (!vote<WV>(busy)) break;
     kv_round<U, KW>(a, sg, o, scrub, hybrid, max_retry, st, muts, cp_p[0][w], cp_l[0][w], cp_p[1][w], cp_l[1][w], lane,
                     skip_len, ms, cp_stage[w]);
   }
@@ -1125,6 +1043,9 @@ __global__ __launch_bounds__(B) __attribute__((amdgpu_waves_per_eu(OCC))) void k
   }
 }
 
+#undef KV_CHUNK_STEP
+#undef KV_ANY_BUSY
+
 // CUs a stream's kernels may occupy: the popcount of its CU mask (the whole device for an unmasked
 // stream; a runtime query, no device round trip)
 int stream_cus(hipStream_t s) {
@@ -1142,25 +1063,32 @@ int stream_cus(hipStream_t s) {
   return n;
 }
 
+// The grid of a resident launch (every workgroup walks its rows to the end: the fused grid, the server):
+// one 256-thread workgroup per 512 rows, at most `wpc` per CU the launch stream may use, so a CU-masked
+// stream (hipExtStreamCreateWithCUMask) gets no second wave.  SPL_KVS_FUSED_WG_PER_CU overrides wpc.
+dim3 resident_grid(long rows, hipStream_t s, int wpc) {
+  static const int wpc_env = env_int("SPL_KVS_FUSED_WG_PER_CU", 0);
+  const long need = (rows + 2 * 256 - 1) / (2 * 256);
+  const long cap = (long)stream_cus(s) * (wpc_env > 0 ? wpc_env : wpc);
+  return dim3((unsigned)(need < cap ? need : cap));
+}
+
+// The kv_round flags of the fused and server grids, read once per process (A/B knobs)
+int kv_flags() {
+  static const int flags = (env_int("SPL_KVS_SKIP_LEN", 1) ? kKvSkipLen : 0) |
+                           (env_int("SPL_KVS_COPY_DMA", 1) ? kKvCopyDma : 0) |
+                           (env_int("SPL_KVS_PAD_OUT", 1) ? kKvPadOut : 0);
+  return flags;
+}
+
 // Launch the fused grid over `tab` (rows: an upper bound of the live rows); mode 2 with 16-B keys
 // holds them in 4 words at 3 workgroups per CU, otherwise 16 words at 2
+// (measured and removed: 4 workgroups per CU at <= 128 VGPRs, 34 spilled: 4.43 vs 4.84 G ops/s,
+// profiles/r4k/kv_fused3.out)
 int launch_fused(spl_arena_t a, const FSegs& tab, long rows, int mode, int max_retry, uint64_t* stats,
                  hipStream_t s, unsigned long long* claim = nullptr, uint32_t tag = 0, int sched_set = -1) {
   if (rows <= 0) return 0;
-  // (measured and removed: 4 workgroups per CU at <= 128 VGPRs, 34 spilled: 4.43 vs 4.84 G ops/s,
-  // profiles/r4k/kv_fused3.out)
   const bool kw4 = mode >= 2 && tab.ks == 16;
-  static const int wpc_env = env_int("SPL_KVS_FUSED_WG_PER_CU", 0);
-  const int wpc = wpc_env > 0 ? wpc_env : kw4 ? 3 : 2;
-  const long need = (rows + 2 * 256 - 1) / (2 * 256);
-  // the grid is resident (every workgroup walks its lane stream to the end): sized to the CUs the
-  // launch stream may use, so a CU-masked stream (hipExtStreamCreateWithCUMask) gets no second wave
-  const long cap = (long)stream_cus(s) * wpc;
-  const dim3 g((unsigned)(need < cap ? need : cap));
-  // SPL_KVS_SKIP_LEN (A/B knob): kv_round flags
-  static const int skip_len = (env_int("SPL_KVS_SKIP_LEN", 1) ? kKvSkipLen : 0) |
-                              (env_int("SPL_KVS_COPY_DMA", 1) ? kKvCopyDma : 0) |
-                              (env_int("SPL_KVS_PAD_OUT", 1) ? kKvPadOut : 0);
   // segments with an output map (direct routed responses) take the OI form of the grid
   bool oi = false;
   for (int q = 0; q < tab.n; ++q) oi |= tab.s[q].oidx != nullptr;
@@ -1169,40 +1097,24 @@ int launch_fused(spl_arena_t a, const FSegs& tab, long rows, int mode, int max_r
   // 0 = fixed lane streams with the per-round workgroup barrier.  KV-only 4.97-4.99 / 4.97-5.00 /
   // 4.74-4.84 G ops/s (profiles/r6/kv_dyn_chunks.jsonl)
   static const int sched_env = env_int("SPL_KVS_SCHED", kSchedWaves);
-  const int sched = sched_set >= 0 ? sched_set : sched_env;  // spl_kvs_set_sched, else the environment
+  int sched = sched_set >= 0 ? sched_set : sched_env;  // spl_kvs_set_sched, else the environment
   static const long dchunk = std::max(512, env_int("SPL_KVS_CHUNK", 4096));
   static const int ddiv = std::max(1, env_int("SPL_KVS_CHUNK_DIV", 2));
-  if (kw4 && sched == kSchedChunks && claim && rows < (1L << 31) - (1L << 20)) {
-    if (oi)
-      hipLaunchKernelGGL((k_kv_fused<2, 256, 4, 3, true, kSchedChunks>), g, dim3(256), 0, s, a, tab, max_retry, stats,
-                         skip_len, claim, tag, dchunk, ddiv);
-    else
-      hipLaunchKernelGGL((k_kv_fused<2, 256, 4, 3, false, kSchedChunks>), g, dim3(256), 0, s, a, tab, max_retry,
-                         stats, skip_len, claim, tag, dchunk, ddiv);
-  } else if (kw4 && sched == kSchedWaves) {
-    if (oi)
-      hipLaunchKernelGGL((k_kv_fused<2, 256, 4, 3, true, kSchedWaves>), g, dim3(256), 0, s, a, tab, max_retry, stats,
-                         skip_len, nullptr, 0u, 0L, 1);
-    else
-      hipLaunchKernelGGL((k_kv_fused<2, 256, 4, 3, false, kSchedWaves>), g, dim3(256), 0, s, a, tab, max_retry,
-                         stats, skip_len, nullptr, 0u, 0L, 1);
-  } else if (kw4 && oi)
-    hipLaunchKernelGGL((k_kv_fused<2, 256, 4, 3, true>), g, dim3(256), 0, s, a, tab, max_retry, stats, skip_len,
-                       nullptr, 0u, 0L, 1);
-  else if (kw4)
-    hipLaunchKernelGGL((k_kv_fused<2, 256, 4, 3>), g, dim3(256), 0, s, a, tab, max_retry, stats, skip_len, nullptr,
-                       0u, 0L, 1);
-  else if (oi && sched == kSchedWaves)
-    hipLaunchKernelGGL((k_kv_fused<2, 256, 16, 1, true, kSchedWaves>), g, dim3(256), 0, s, a, tab, max_retry, stats,
-                       skip_len, nullptr, 0u, 0L, 1);
-  else if (oi)
-    hipLaunchKernelGGL((k_kv_fused<2, 256, 16, 1, true>), g, dim3(256), 0, s, a, tab, max_retry, stats, skip_len,
-                       nullptr, 0u, 0L, 1);
-  else if (sched == kSchedWaves)
-    hipLaunchKernelGGL((k_kv_fused<2, 256, 16, 1, false, kSchedWaves>), g, dim3(256), 0, s, a, tab, max_retry, stats,
-                       skip_len, nullptr, 0u, 0L, 1);
-  else
-    hipLaunchKernelGGL((k_kv_fused<2, 256>), g, dim3(256), 0, s, a, tab, max_retry, stats, skip_len, nullptr, 0u, 0L, 1);
+  // the chunk schedule exists for 4-word keys, needs its claim word and 32-bit rows; without them, and for
+  // any unknown value, the barrier form
+  const bool chunks = sched == kSchedChunks && kw4 && claim && rows < (1L << 31) - (1L << 20);
+  if (sched != kSchedWaves) sched = chunks ? kSchedChunks : kSchedBarrier;
+  using Kern = void (*)(spl_arena_t, FSegs, int, uint64_t*, int, unsigned long long*, uint32_t, long, int);
+  static const Kern kern[2][2][3] = {  // [4-word keys][OI][SCHED]
+      {{k_kv_fused<2, 256, 16, 1, false, kSchedBarrier>, nullptr, k_kv_fused<2, 256, 16, 1, false, kSchedWaves>},
+       {k_kv_fused<2, 256, 16, 1, true, kSchedBarrier>, nullptr, k_kv_fused<2, 256, 16, 1, true, kSchedWaves>}},
+      {{k_kv_fused<2, 256, 4, 3, false, kSchedBarrier>, k_kv_fused<2, 256, 4, 3, false, kSchedChunks>,
+        k_kv_fused<2, 256, 4, 3, false, kSchedWaves>},
+       {k_kv_fused<2, 256, 4, 3, true, kSchedBarrier>, k_kv_fused<2, 256, 4, 3, true, kSchedChunks>,
+        k_kv_fused<2, 256, 4, 3, true, kSchedWaves>}}};
+  hipLaunchKernelGGL(kern[kw4][oi][sched], resident_grid(rows, s, kw4 ? 3 : 2), dim3(256), 0, s, a, tab, max_retry,
+                     stats, kv_flags(), chunks ? claim : nullptr, chunks ? tag : 0u, chunks ? dchunk : 0L,
+                     chunks ? ddiv : 1);
   return (int)hipGetLastError();
 }
 
@@ -1501,10 +1413,10 @@ int spl_arena_init_slots(spl_arena_t a, hipStream_t s) {
 
 namespace {
 
-// Batched set / get launches (every public entry point and the stream fan-outs go through these).
-// Two forms each, chosen once per process: SPLINTER_ARENA_COOP (sets) / SPLINTER_ARENA_COOP_GET
-// (gets) = 2 (default: write-through rows, acquire-free sc1 reads) or 1 (plain rows + one release
-// per round / one agent acquire per round).  The measured-and-rejected forms (single-op, non-carried
+// Batched set / get launches of k_kv_batch (every public entry point and the stream fan-outs go through
+// these).  Two forms each, chosen once per process: SPLINTER_ARENA_COOP (sets) / SPLINTER_ARENA_COOP_GET
+// (gets) = 2 (default, kCohSc1: write-through rows, acquire-free sc1 reads) or 1 (kCohFence: plain rows +
+// one release per round / one agent acquire per round).  The measured-and-rejected forms (single-op, non-carried
 // rounds, 512-thread blocks, U = 1/4/8, batched claims, pipelined copies) are gone; their A/B
 // history is in profiles/r1_* .. r3_*.
 constexpr int kU = 2, kB = 256;
@@ -1517,12 +1429,9 @@ int launch_set(const spl_arena_t& a, const char* keys, int kstride, const uint8_
   if (seg.counts && seg.cap <= 0) return (int)hipErrorInvalidValue;
   static const int coop = env_int("SPLINTER_ARENA_COOP", 2);
   const dim3 g(grid_for_b((n + kU - 1) / kU, kB));
-  if (coop == 1)
-    hipLaunchKernelGGL((k_set_carry<kU, kB, false>), g, dim3(kB), 0, s, a, keys, kstride, vals, vstride, lens, n,
-                       status, max_retry, stats, seg);
-  else
-    hipLaunchKernelGGL((k_set_carry<kU, kB, true>), g, dim3(kB), 0, s, a, keys, kstride, vals, vstride, lens, n,
-                       status, max_retry, stats, seg);
+  auto* kern = coop == 1 ? k_kv_batch<kU, kB, kKindSet, kCohFence> : k_kv_batch<kU, kB, kKindSet, kCohSc1>;
+  hipLaunchKernelGGL(kern, g, dim3(kB), 0, s, a, keys, kstride, (uint8_t*)vals, vstride, (uint32_t*)lens, n, status,
+                     max_retry, stats, seg);
   return (int)hipGetLastError();
 }
 
@@ -1533,12 +1442,9 @@ int launch_get(const spl_arena_t& a, const char* keys, int kstride, uint8_t* out
   if (seg.counts && seg.cap <= 0) return (int)hipErrorInvalidValue;
   static const int coop = env_int("SPLINTER_ARENA_COOP_GET", 2);
   const dim3 g(grid_for_b((n + kU - 1) / kU, kB));
-  if (coop == 1)
-    hipLaunchKernelGGL((k_get_carry<kU, kB, false>), g, dim3(kB), 0, s, a, keys, kstride, out, ostride, out_lens, n,
-                       status, max_retry, stats, seg);
-  else
-    hipLaunchKernelGGL((k_get_carry<kU, kB, true>), g, dim3(kB), 0, s, a, keys, kstride, out, ostride, out_lens, n,
-                       status, max_retry, stats, seg);
+  auto* kern = coop == 1 ? k_kv_batch<kU, kB, kKindGet, kCohFence> : k_kv_batch<kU, kB, kKindGet, kCohSc1>;
+  hipLaunchKernelGGL(kern, g, dim3(kB), 0, s, a, keys, kstride, out, ostride, out_lens, n, status, max_retry, stats,
+                     seg);
   return (int)hipGetLastError();
 }
 
@@ -1570,24 +1476,6 @@ int spl_arena_get_seg(spl_arena_t a, const char* keys, int kstride, uint8_t* out
   if (seg_counts && (seg_cap <= 0 || n % seg_cap)) return (int)hipErrorInvalidValue;
   return launch_get(a, keys, kstride, out, ostride, out_lens, n, status, max_retry, stats,
                     Seg{seg_counts, seg_cap > 0 ? seg_cap : 1}, s);
-}
-
-// In-place rows (idx: client op indices; live rows: the first *count of them): the own-shard ops of
-// a routed step run on the client's own arrays (parallel/xroute.py).
-int spl_arena_set_idx(spl_arena_t a, const char* keys, int kstride, const uint8_t* vals, int vstride,
-                      const uint32_t* lens, const int32_t* idx, const int32_t* count, long n, int32_t* status,
-                      int max_retry, uint64_t* stats, hipStream_t s) {
-  if (!idx || !count) return (int)hipErrorInvalidValue;
-  return launch_set(a, keys, kstride, vals, vstride, lens, n, status, max_retry, stats, Seg{count, n > 0 ? n : 1, 0, idx},
-                    s);
-}
-
-int spl_arena_get_idx(spl_arena_t a, const char* keys, int kstride, uint8_t* out, int ostride, uint32_t* out_lens,
-                      const int32_t* idx, const int32_t* count, long n, int32_t* status, int max_retry,
-                      uint64_t* stats, hipStream_t s) {
-  if (!idx || !count) return (int)hipErrorInvalidValue;
-  return launch_get(a, keys, kstride, out, ostride, out_lens, n, status, max_retry, stats,
-                    Seg{count, n > 0 ? n : 1, 0, idx}, s);
 }
 
 int spl_arena_unset(spl_arena_t a, const char* keys, int kstride, long n, int32_t* status, int max_retry,
@@ -1733,6 +1621,36 @@ struct KvStreams {
   }
 };
 
+// The set / get segment of a plain step: n rows of the client's arrays, row for row, or through idx
+FSeg set_fseg(const char* keys, const uint8_t* vals, int vstride, const uint32_t* lens, int32_t* status, long n,
+              const int32_t* idx = nullptr) {
+  return FSeg{keys, (uint8_t*)vals, (uint32_t*)lens, status, idx, nullptr, n, vstride, 1};
+}
+FSeg get_fseg(const char* keys, uint8_t* out, int ostride, uint32_t* lens, int32_t* status, long n,
+              const int32_t* idx = nullptr) {
+  return FSeg{keys, out, lens, status, idx, nullptr, n, ostride, 0};
+}
+
+// Mode 0, one kind: client stream w of the kind's ns takes rows [total * w / ns, total * (w + 1) / ns),
+// waits on the step's start event, gets its launches from launch(stream, lo, hi) and records its done
+// event, which the origin stream then waits on.
+template <class Launch>
+int fan_out(KvStreams* k, hipStream_t origin, bool set, long total, Launch&& launch) {
+  const int ns = set ? k->nw : k->nr;
+  for (int w = 0; w < ns; ++w) {
+    const long lo = total * w / ns, hi = total * (w + 1) / ns;
+    if (hi <= lo) continue;
+    const int i = set ? w : k->nw + w;
+    hipStream_t st = k->s[i];
+    (void)hipStreamWaitEvent(st, k->start, 0);
+    const int rc = launch(st, lo, hi);
+    if (rc) return rc;
+    (void)hipEventRecord(k->done[i], st);
+    (void)hipStreamWaitEvent(origin, k->done[i], 0);
+  }
+  return 0;
+}
+
 // The server grid of one step (mode 3), launched on the origin stream after every client stream's
 // post has been enqueued (a post queued behind the server dispatch on a shared hardware queue would
 // otherwise wait for the server's end).  A client stream posts once ITS preceding work is done; the
@@ -1761,11 +1679,6 @@ int kvs_step_async(KvStreams* k, spl_arena_t a, hipStream_t origin, const FSeg& 
     e = hipStreamWriteValue64(k->s[i], &k->ctl->door[i], seq, 0);
     if (e != hipSuccess) return (int)e;
   }
-  static const int wpc_env = env_int("SPL_KVS_FUSED_WG_PER_CU", 0);
-  const int wpc = wpc_env > 0 ? wpc_env : 3;
-  const long rows = sset.n + sget.n;
-  const long need = (rows + 2 * 256 - 1) / (2 * 256);
-  const long cap = (long)stream_cus(origin) * wpc;  // resident grid: the CUs the origin stream may use
   static const long chunk = [] {  // rows per claim: 4 rounds of a 256-thread workgroup at 2 ops per lane
     const int c = env_int("SPL_KVS_ASYNC_CHUNK", 2048);
     return (long)(c >= 512 ? c : 512);
@@ -1773,15 +1686,9 @@ int kvs_step_async(KvStreams* k, spl_arena_t a, hipStream_t origin, const FSeg& 
   static const uint64_t wait_ticks = (uint64_t)env_int("SPL_KVS_ASYNC_WAIT_MS", 2000) * 100000ull;  // 100 MHz
   static const int spread = env_int("SPL_KVS_ASYNC_SPREAD", 1);
   static const int wv = env_int("SPL_KVS_ASYNC_WV", 1);
-  const dim3 grid((unsigned)(need < cap ? need : cap));
-  const int flags = (env_int("SPL_KVS_SKIP_LEN", 1) ? kKvSkipLen : 0) | (env_int("SPL_KVS_COPY_DMA", 1) ? kKvCopyDma : 0) |
-                    (env_int("SPL_KVS_PAD_OUT", 1) ? kKvPadOut : 0);
-  if (wv)
-    hipLaunchKernelGGL((k_kv_server<2, 256, 4, 3, true>), grid, dim3(256), 0, origin, a, sset, sget, nw, nr, ks, k->ctl,
-                       seq, chunk, wait_ticks, spread, max_retry, stats, flags);
-  else
-    hipLaunchKernelGGL((k_kv_server<2, 256, 4, 3>), grid, dim3(256), 0, origin, a, sset, sget, nw, nr, ks, k->ctl, seq,
-                       chunk, wait_ticks, spread, max_retry, stats, flags);
+  auto* kern = wv ? k_kv_server<2, 256, 4, 3, true> : k_kv_server<2, 256, 4, 3, false>;
+  hipLaunchKernelGGL(kern, resident_grid(sset.n + sget.n, origin, 3), dim3(256), 0, origin, a, sset, sget, nw, nr, ks,
+                     k->ctl, seq, chunk, wait_ticks, spread, max_retry, stats, kv_flags());
   e = hipGetLastError();
   if (e != hipSuccess) return (int)e;
   (void)hipEventRecord(k->srv_done, origin);
@@ -1891,46 +1798,31 @@ int spl_kvs_step(void* h, spl_arena_t a, hipStream_t origin, const char* skeys, 
   const int fused = k->fused;
   if (fused == 3 && n_set + n_get > 0 && kstride == 16 && k->nw + k->nr <= kAsyncSegs) {
     if ((vstride & 15) || (ostride & 15)) return (int)hipErrorInvalidValue;
-    const FSeg sset{skeys, (uint8_t*)svals, (uint32_t*)slens, sstatus, nullptr, nullptr, n_set, vstride, 1};
-    const FSeg sget{gkeys, gout, glens, gstatus, nullptr, nullptr, n_get, ostride, 0};
-    return kvs_step_async(k, a, origin, sset, sget, kstride, max_retry, stats);
+    return kvs_step_async(k, a, origin, set_fseg(skeys, svals, vstride, slens, sstatus, n_set),
+                          get_fseg(gkeys, gout, ostride, glens, gstatus, n_get), kstride, max_retry, stats);
   }
   if (fused && n_set + n_get > 0) {
     if ((kstride & 15) || kstride > 64 || (vstride & 15) || (ostride & 15)) return (int)hipErrorInvalidValue;
     FSegs tab{};
     tab.ks = kstride;
-    if (n_set > 0)
-      tab.s[tab.n++] = FSeg{skeys, (uint8_t*)svals, (uint32_t*)slens, sstatus, nullptr, nullptr, n_set, vstride, 1};
-    if (n_get > 0) tab.s[tab.n++] = FSeg{gkeys, gout, glens, gstatus, nullptr, nullptr, n_get, ostride, 0};
+    if (n_set > 0) tab.s[tab.n++] = set_fseg(skeys, svals, vstride, slens, sstatus, n_set);
+    if (n_get > 0) tab.s[tab.n++] = get_fseg(gkeys, gout, ostride, glens, gstatus, n_get);
     uint32_t tag = 0;
     unsigned long long* cw = k->claim_slot(&tag);
     return launch_fused(a, tab, n_set + n_get, fused, max_retry, stats, origin, cw, tag, k->sched);
   }
   hipError_t e = hipEventRecord(k->start, origin);
   if (e != hipSuccess) return (int)e;
-  const int nw = n_set > 0 ? k->nw : 0, nr = n_get > 0 ? k->nr : 0;
-  for (int w = 0; w < nw; ++w) {
-    const long b = n_set * w / nw, end = n_set * (w + 1) / nw;
-    if (end <= b) continue;
-    hipStream_t st = k->s[w];
-    (void)hipStreamWaitEvent(st, k->start, 0);
-    int rc = spl_arena_set(a, skeys + b * (long)kstride, kstride, svals + b * (long)vstride, vstride, slens + b,
-                           end - b, sstatus ? sstatus + b : nullptr, max_retry, stats, st);
-    if (rc) return rc;
-    (void)hipEventRecord(k->done[w], st);
-    (void)hipStreamWaitEvent(origin, k->done[w], 0);
-  }
-  for (int r = 0; r < nr; ++r) {
-    const long b = n_get * r / nr, end = n_get * (r + 1) / nr;
-    if (end <= b) continue;
-    hipStream_t st = k->s[k->nw + r];
-    (void)hipStreamWaitEvent(st, k->start, 0);
-    int rc = spl_arena_get(a, gkeys + b * (long)kstride, kstride, gout ? gout + b * (long)ostride : nullptr, ostride,
-                           glens ? glens + b : nullptr, end - b, gstatus ? gstatus + b : nullptr, max_retry, stats, st);
-    if (rc) return rc;
-    (void)hipEventRecord(k->done[k->nw + r], st);
-    (void)hipStreamWaitEvent(origin, k->done[k->nw + r], 0);
-  }
+  int rc = fan_out(k, origin, true, n_set, [&](hipStream_t st, long b, long end) {
+    return spl_arena_set(a, skeys + b * (long)kstride, kstride, svals + b * (long)vstride, vstride, slens + b, end - b,
+                         sstatus ? sstatus + b : nullptr, max_retry, stats, st);
+  });
+  if (rc) return rc;
+  rc = fan_out(k, origin, false, n_get, [&](hipStream_t st, long b, long end) {
+    return spl_arena_get(a, gkeys + b * (long)kstride, kstride, gout ? gout + b * (long)ostride : nullptr, ostride,
+                         glens ? glens + b : nullptr, end - b, gstatus ? gstatus + b : nullptr, max_retry, stats, st);
+  });
+  if (rc) return rc;
   return (int)hipGetLastError();
 }
 
@@ -1963,10 +1855,10 @@ int spl_kvs_step_xr(void* h, spl_arena_t a, hipStream_t origin, const spl_xr_ste
       for (int sg = 0; sg < W; ++sg) {
         FSeg f;
         if (sg == r) {
-          f = set ? FSeg{x->skeys, (uint8_t*)x->svals, (uint32_t*)x->slens, x->sstatus, lidx, nullptr, 0, x->svstride, 1}
-                  : FSeg{x->gkeys, x->gout, x->glens, x->gstatus, lidx, nullptr, 0, x->gostride, 0};
+          const long n = lidx ? cap : n_own;
+          f = set ? set_fseg(x->skeys, x->svals, x->svstride, x->slens, x->sstatus, n, lidx)
+                  : get_fseg(x->gkeys, x->gout, x->gostride, x->glens, x->gstatus, n, lidx);
           f.count = lidx ? x->own_counts + r * 2 + kind : nullptr;
-          f.n = lidx ? cap : n_own;
         } else {
           uint8_t* q = (uint8_t*)x->req[sg];
           uint8_t* p = (uint8_t*)x->resp[sg];
@@ -2004,12 +1896,7 @@ int spl_kvs_step_xr(void* h, spl_arena_t a, hipStream_t origin, const spl_xr_ste
     }
     const long total = start[W];
     if (total <= 0) continue;
-    const int ns = set ? k->nw : k->nr;
-    for (int w = 0; w < ns; ++w) {
-      const long lo = total * w / ns, hi = total * (w + 1) / ns;
-      if (hi <= lo) continue;
-      hipStream_t st = k->s[set ? w : k->nw + w];
-      (void)hipStreamWaitEvent(st, k->start, 0);
+    const int frc = fan_out(k, origin, set, total, [&](hipStream_t st, long lo, long hi) {
       for (int sg = 0; sg < W; ++sg) {
         const long b0 = lo > start[sg] ? lo - start[sg] : 0;
         const long b1 = (hi < start[sg + 1] ? hi : start[sg + 1]) - start[sg];
@@ -2040,10 +1927,9 @@ int spl_kvs_step_xr(void* h, spl_arena_t a, hipStream_t origin, const spl_xr_ste
         }
         if (rc) return rc;
       }
-      const int ev = set ? w : k->nw + w;
-      (void)hipEventRecord(k->done[ev], st);
-      (void)hipStreamWaitEvent(origin, k->done[ev], 0);
-    }
+      return 0;
+    });
+    if (frc) return frc;
   }
   return (int)hipGetLastError();
 }

@@ -115,15 +115,6 @@ int spl_format_keys(char *out, int kstride, const uint64_t *ids, uint64_t first,
 int spl_format_values(uint8_t *out, int vstride, uint32_t *lens, const uint64_t *ids, uint64_t first, long n,
                       uint32_t ver, uint32_t len, hipStream_t stream);
 
-/* In-place rows: row i of the launch is client op idx[i] and only the first *count rows are live
- * (the own-shard ops of a routed step run on the client's arrays). */
-int spl_arena_set_idx(spl_arena_t a, const char *keys, int kstride, const uint8_t *vals, int vstride,
-                      const uint32_t *lens, const int32_t *idx, const int32_t *count, long n, int32_t *status,
-                      int max_retry, uint64_t *stats, hipStream_t stream);
-int spl_arena_get_idx(spl_arena_t a, const char *keys, int kstride, uint8_t *out, int ostride, uint32_t *out_lens,
-                      const int32_t *idx, const int32_t *count, long n, int32_t *status, int max_retry,
-                      uint64_t *stats, hipStream_t stream);
-
 /* ---- routed exchange (route_kernels.hip; parallel/xroute.py) ------------------------------------
  * Pack one kind of a client batch straight into the owners' request blocks: shard =
  * ((fnv1a >> 40) & 0xFFFFFF) % world; blk[d] = base of the block for owner d (device table),

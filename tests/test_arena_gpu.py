@@ -258,7 +258,7 @@ def test_racing_inserts_no_duplicates(uniq):
 
 def test_hot_keys_carried_retries(uniq):
     """64 hot keys, 40k sets racing 40k gets on two streams: contended ops are carried into
-    later rounds (k_set_carry / k_get_carry); every op ends ok or EAGAIN after its bounded
+    later rounds (k_kv_batch, both kinds); every op ends ok or EAGAIN after its bounded
     attempts, the stats add up, every successful read is an intact value of its key, and the
     final value of each key is one of the versions written to it."""
     import torch
@@ -441,7 +441,7 @@ def test_cross_process_reader_races_gpu_writers(uniq):
 
 def test_acquire_free_get_cross_xcd_hot_keys(uniq):
     """Pins the coherence assumption of the default acquire-free get (SPLINTER_ARENA_COOP_GET=2,
-    arena_kernels.hip k_get_carry FAST): writer and reader workgroups of large grids are dealt
+    arena_kernels.hip kv_round kCohSc1, as k_kv_batch runs it): writer and reader workgroups of large grids are dealt
     round-robin over all 8 XCDs, so every hot key below is written and read from different XCDs
     at once.  Every returned row (not a sample) must be one intact version: the 'ver:<v>' header,
     the id and the fill byte 'A' + v % 26 all agree."""
