@@ -15,7 +15,8 @@
 // that share A rows run on one XCD and reuse its L2.
 // Epilogue: accumulators go through LDS in fp32, then each thread owns
 // 16-B output chunks, so every fused epilogue (residual add, SwiGLU, RoPE)
-// works on whole rows with vector loads/stores.
+// works on whole rows with vector loads/stores.  The image -> output step is one
+// text for this kernel and the 256x256 one (gemm_epilogue128_body.hpp).
 // Shared with gemm384.hip and gemm_rln.hip: the bf16 and lane helpers (bf16_util.hpp), the tile order,
 // SwiGLU and allow_lds (gemm_tile.hpp).
 #include <hip/hip_runtime.h>
@@ -67,49 +68,8 @@ struct EpiArgs {
   int rope_cols;         // columns (from 0) that get RoPE (q|k = 1536)
   long M;
   int gn;                // n-tiles per band of the tile order (remap_tile)
-  // LayerNorm fold (nomic_api.h NOMIC_EPI_*_FOLD / RES_*STATS)
-  const float2* pin;     // [M][np] (mean, M2) 128-column partials of the rows of A (fold) or of
-  int np;                //   res (RES_LN_STATS), as a stats-mode producer wrote them
-  float eps;
-  const float* c1;       // [N] W' 1       (fold)
-  const float* c2;       // [N] W b        (fold)
-  const uint16_t* lng;   // [N] LN gamma / beta of res (RES_LN_STATS)
-  const uint16_t* lnb;
-  float2* part;          // [M][N/128] (mean, M2) of out's rows per 128 columns (RES_*STATS)
   int nsplit;            // k_gemm256: tiles at the end of the dispatch order run as two half-tile blocks
 };
-
-constexpr bool is_fold(int m) { return m == NOMIC_EPI_ROPE_FOLD || m == NOMIC_EPI_SWIGLU_FOLD; }
-constexpr bool is_stats(int m) { return m == NOMIC_EPI_RES_STATS || m == NOMIC_EPI_RES_LN_STATS; }
-constexpr bool is_rope(int m) { return m == NOMIC_EPI_ROPE || m == NOMIC_EPI_ROPE_FOLD; }
-constexpr bool is_swiglu(int m) { return m == NOMIC_EPI_SWIGLU || m == NOMIC_EPI_SWIGLU_FOLD; }
-constexpr bool is_rowstore(int m) { return m == NOMIC_EPI_STORE || m == NOMIC_EPI_RESIDUAL || is_stats(m); }
-constexpr bool needs_rowstats(int m) { return is_fold(m) || m == NOMIC_EPI_RES_LN_STATS; }
-
-// LN fold of one GEMM output: rstd (acc - mean c1[n]) + c2[n]  (== LN(a) . w for the unfolded w)
-__device__ __forceinline__ float fold(float acc, float2 st, float c1, float c2) {
-  return st.y * (acc - st.x * c1) + c2;
-}
-
-// sum over the 16 lanes of a row group (lanes 16k .. 16k+15) on the DPP crossbar (no LDS
-// traffic, unlike ds_bpermute): quad_perm [1,0,3,2] and [2,3,0,1] give every lane its quad's sum,
-// row_half_mirror (lane i <-> 7-i) the 8-lane sum, row_mirror (i <-> 15-i) the 16-lane sum
-template <int CTRL>
-__device__ __forceinline__ float dpp_add(float v) {
-  return v + __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), CTRL, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float sum16(float v) {
-  v = dpp_add<0xB1>(v);
-  v = dpp_add<0x4E>(v);
-  v = dpp_add<0x141>(v);
-  return dpp_add<0x140>(v);
-}
-
-__device__ __forceinline__ void load8f(const float* p, float (&o)[8]) {  // p: 32-B aligned
-  const float4 a = *(const float4*)p, b = *(const float4*)(p + 4);
-  o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w;
-  o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
-}
 
 using spl::swiglu;  // gemm_tile.hpp
 
@@ -124,7 +84,6 @@ __global__ __launch_bounds__(kThreads, 2) void k_gemm_nt(const uint16_t* __restr
   const long m0 = (long)mt * BM, n0 = (long)nt * BN;
   const int wm = wave >> 1, wn = wave & 1;
 
-
   f32x4 acc[4][4];
 #pragma unroll
   for (int i = 0; i < 4; ++i)
@@ -132,55 +91,10 @@ __global__ __launch_bounds__(kThreads, 2) void k_gemm_nt(const uint16_t* __restr
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   const int nk = K / BK;
-  // LN modes: the epilogue's per-column vectors are fixed per thread (its column group does not
-  // change with the row iteration), so they are loaded here, ahead of the main loop, and the
-  // block's 128 row statistics are combined from the producer's partials into LDS behind the
-  // main loop (one float2 per row, past the staging / epilogue image: same __shared__ array)
-  float cv1[8], cv2[8], cv3[8], cv4[8];
-  uint4 lg = {}, lb = {};
-  float2 pr[8];
-  float2* S = (float2*)(smem + kLdsBytes);
-  if constexpr (needs_rowstats(MODE)) {
-    const long m = m0 + (tid & 127);
-    const long mr = m < ep.M ? m : ep.M - 1;
-    if (tid < 128) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) pr[i] = i < ep.np ? ep.pin[mr * ep.np + i] : make_float2(0.f, 0.f);
-    }
-  }
-  if constexpr (is_rope(MODE) && is_fold(MODE)) {
-    const int head = (tid >> 2) & 1, d0 = (tid & 3) * 8;
-    const int pc = d0 < 16 ? d0 : d0 + 16;
-    const float* c1 = ep.c1 + n0 + head * 64 + pc;
-    const float* c2 = ep.c2 + n0 + head * 64 + pc;
-    load8f(c1, cv1); load8f(c2, cv2); load8f(c1 + 16, cv3); load8f(c2 + 16, cv4);
-  } else if constexpr (is_swiglu(MODE) && is_fold(MODE)) {
-    const int c8 = (tid & 7) * 8, uc = 32 * (c8 >> 4) + (c8 & 15);
-    load8f(ep.c1 + n0 + uc, cv1); load8f(ep.c2 + n0 + uc, cv2);
-    load8f(ep.c1 + n0 + uc + 16, cv3); load8f(ep.c2 + n0 + uc + 16, cv4);
-  } else if constexpr (MODE == NOMIC_EPI_RES_LN_STATS) {
-    const int c8 = (tid & 15) * 8;
-    lg = *(const uint4*)(ep.lng + n0 + c8);
-    lb = *(const uint4*)(ep.lnb + n0 + c8);
-  }
   // LDS: [A0 | B0 | A1 | B1], 16 KB each
   stage_tile(A, lda, m0, 0, smem, wave, lane);
   stage_tile(W, ldw, n0, 0, smem + kTileBytes, wave, lane);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if constexpr (needs_rowstats(MODE)) {
-    if (tid < 128) {  // Chan's combination of equal-size partials (as k_row_stats)
-      float mean = 0.f, m2 = 0.f;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) mean += pr[i].x;  // absent partials are zero
-      mean /= (float)ep.np;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const float d = pr[i].x - mean;
-        if (i < ep.np) m2 += pr[i].y + (float)BN * d * d;
-      }
-      S[tid] = make_float2(mean, rsqrtf(m2 / ((float)BN * (float)ep.np) + ep.eps));
-    }
-  }
   __syncthreads();
 
   const int fr = lane & 15, fq = lane >> 4;
@@ -222,151 +136,9 @@ __global__ __launch_bounds__(kThreads, 2) void k_gemm_nt(const uint16_t* __restr
         E[(wm * 64 + i * 16 + fq * 4 + r) * kEpiStride + wn * 64 + j * 16 + fr] = acc[i][j][r];
   __syncthreads();
 
-  if constexpr (is_rowstore(MODE)) {
-#pragma unroll
-    for (int it = 0; it < (BM * BN / 8) / kThreads; ++it) {
-      const int q = tid + it * kThreads;
-      const int row = q >> 4, c8 = (q & 15) * 8;  // 16 consecutive lanes share a row
-      const long gm = m0 + row;
-      const bool ok = gm < ep.M;
-      if (!is_stats(MODE) && !ok) continue;      // stats modes keep every lane for the shuffles
-      const float4 v0 = *(const float4*)&E[row * kEpiStride + c8];
-      const float4 v1 = *(const float4*)&E[row * kEpiStride + c8 + 4];
-      float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-      if constexpr (MODE != NOMIC_EPI_STORE) {
-        const long gr = ok ? gm : ep.M - 1;
-        const uint4 rr = *(const uint4*)(ep.res + gr * ep.ldr + n0 + c8);
-        const uint32_t rw[4] = {rr.x, rr.y, rr.z, rr.w};
-        float r[8];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          r[2 * e] = bf2f((uint16_t)(rw[e] & 0xffff));
-          r[2 * e + 1] = bf2f((uint16_t)(rw[e] >> 16));
-        }
-        if constexpr (MODE == NOMIC_EPI_RES_LN_STATS) {
-          const float2 st = S[row];
-          const uint32_t gw[4] = {lg.x, lg.y, lg.z, lg.w}, bw[4] = {lb.x, lb.y, lb.z, lb.w};
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            const uint32_t g2 = gw[e >> 1], b2 = bw[e >> 1];
-            const float gf = bf2f((uint16_t)(e & 1 ? g2 >> 16 : g2 & 0xffff));
-            const float bf = bf2f((uint16_t)(e & 1 ? b2 >> 16 : b2 & 0xffff));
-            r[e] = (r[e] - st.x) * st.y * gf + bf;
-          }
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] += r[e];
-      }
-      uint4 o;
-      o.x = pk2(v[0], v[1]);
-      o.y = pk2(v[2], v[3]);
-      o.z = pk2(v[4], v[5]);
-      o.w = pk2(v[6], v[7]);
-      if (ok) *(uint4*)(ep.out + gm * ep.ldo + n0 + c8) = o;
-      if constexpr (is_stats(MODE)) {
-        // statistics of the stored (bf16-rounded) values: the consumer folds against exactly them
-        const uint32_t ow[4] = {o.x, o.y, o.z, o.w};
-        float vr[8], sm = 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          vr[e] = bf2f((uint16_t)(e & 1 ? ow[e >> 1] >> 16 : ow[e >> 1] & 0xffff));
-          sm += vr[e];
-        }
-        const float mean = sum16(sm) * (1.f / BN);
-        float m2 = 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) m2 += (vr[e] - mean) * (vr[e] - mean);
-        m2 = sum16(m2);
-        if (ok && (lane & 15) == 0) ep.part[gm * ntiles + nt] = make_float2(mean, m2);
-      }
-    }
-  } else if constexpr (is_swiglu(MODE)) {
-    // block columns: [up16 | gate16] x 4 (pack_upgate) of output columns nt*64 + 0..63
-#pragma unroll
-    for (int it = 0; it < (BM * 64 / 8) / kThreads; ++it) {
-      const int q = tid + it * kThreads;
-      const int row = q >> 3, c8 = (q & 7) * 8;
-      const long gm = m0 + row;
-      if (gm >= ep.M) continue;
-      const int uc = 32 * (c8 >> 4) + (c8 & 15);
-      float o[8];
-      float2 st;
-      if constexpr (is_fold(MODE)) st = S[row];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        float up = E[row * kEpiStride + uc + e];
-        float g = E[row * kEpiStride + uc + 16 + e];
-        if constexpr (is_fold(MODE)) {
-          up = fold(up, st, cv1[e], cv2[e]);
-          g = fold(g, st, cv3[e], cv4[e]);
-        }
-        o[e] = swiglu(up, g);
-      }
-      uint4 w;
-      w.x = pk2(o[0], o[1]);
-      w.y = pk2(o[2], o[3]);
-      w.z = pk2(o[4], o[5]);
-      w.w = pk2(o[6], o[7]);
-      *(uint4*)(ep.out + gm * ep.ldo + (long)nt * 64 + c8) = w;
-    }
-  } else if constexpr (is_rope(MODE)) {
-    // two 64-wide heads per block; NEOX rotation pairs (d, d + 32)
-#pragma unroll
-    for (int it = 0; it < (BM * 2 * 4) / kThreads; ++it) {
-      const int q = tid + it * kThreads;
-      const int row = q >> 3, head = (q >> 2) & 1, d0 = (q & 3) * 8;
-      const long gm = m0 + row;
-      if (gm >= ep.M) continue;
-      const int cb = head * 64;
-      const long gcol = n0 + cb;
-      const int pc = d0 < 16 ? d0 : d0 + 16;  // pack_qkv: [d0-15 | d32-47 | d16-31 | d48-63]
-      float x1[8], x2[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        x1[e] = E[row * kEpiStride + cb + pc + e];
-        x2[e] = E[row * kEpiStride + cb + pc + 16 + e];
-      }
-      if constexpr (is_fold(MODE)) {
-        const float2 st = S[row];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          x1[e] = fold(x1[e], st, cv1[e], cv2[e]);
-          x2[e] = fold(x2[e], st, cv3[e], cv4[e]);
-        }
-      }
-      if (gcol < ep.rope_cols) {
-        const float* cs = ep.rope + (long)ep.pos[gm] * 64 + d0 * 2;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float c = cs[2 * e], s = cs[2 * e + 1];
-          const float a = x1[e], b = x2[e];
-          x1[e] = a * c - b * s;
-          x2[e] = b * c + a * s;
-        }
-      }
-      uint4 w1, w2;
-      w1.x = pk2(x1[0], x1[1]);
-      w1.y = pk2(x1[2], x1[3]);
-      w1.z = pk2(x1[4], x1[5]);
-      w1.w = pk2(x1[6], x1[7]);
-      w2.x = pk2(x2[0], x2[1]);
-      w2.y = pk2(x2[2], x2[3]);
-      w2.z = pk2(x2[4], x2[5]);
-      w2.w = pk2(x2[6], x2[7]);
-      *(uint4*)(ep.out + gm * ep.ldo + gcol + d0) = w1;
-      *(uint4*)(ep.out + gm * ep.ldo + gcol + d0 + 32) = w2;
-    }
-  } else if constexpr (MODE == NOMIC_EPI_F32) {
-    float* outf = (float*)ep.out;
-#pragma unroll
-    for (int it = 0; it < (BM * BN / 4) / kThreads; ++it) {
-      const int q = tid + it * kThreads;
-      const int row = q >> 5, c4 = (q & 31) * 4;
-      const long gm = m0 + row;
-      if (gm >= ep.M) continue;
-      *(float4*)(outf + gm * ep.ldo + n0 + c4) = *(const float4*)&E[row * kEpiStride + c4];
-    }
-  }
+  constexpr int kEpiCols = BN, kEpiThreads = kThreads;
+  const long mh = m0;
+#include "gemm_epilogue128_body.hpp"  // image rows -> output rows mh .., every mode
 }
 
 // ===========================================================================
@@ -660,6 +432,7 @@ __global__ __launch_bounds__(kThreads2, 1) void k_gemm256(const uint16_t* __rest
   // ---- epilogue: two 128-row halves through the fp32 LDS image ------------
   // (a half-tile block holds its one half in acc[0] and runs the first pass only, on rows of qh)
   float* E = (float*)smem;
+  constexpr int kEpiCols = 256, kEpiThreads = kThreads2;
   const int fq = lane >> 4, fr = lane & 15;
   const long mbase = m0 + (qh > 0 ? 128 : 0);
 #pragma unroll
@@ -677,86 +450,7 @@ __global__ __launch_bounds__(kThreads2, 1) void k_gemm256(const uint16_t* __rest
             E[(wr * 64 + i * 16 + fq * 4 + r) * kEpi2Stride + qn * 128 + wn * 32 + j * 16 + fr] = acc[qm][qn][i][j][r];
     __syncthreads();
     const long mh = mbase + qm * 128;
-    if constexpr (MODE == NOMIC_EPI_STORE || MODE == NOMIC_EPI_RESIDUAL) {
-#pragma unroll
-      for (int it = 0; it < (128 * 256 / 8) / kThreads2; ++it) {
-        const int q = tid + it * kThreads2;
-        const int row = q >> 5, c8 = (q & 31) * 8;
-        const long gm = mh + row;
-        if (gm >= ep.M) continue;
-        const float4 v0 = *(const float4*)&E[row * kEpi2Stride + c8];
-        const float4 v1 = *(const float4*)&E[row * kEpi2Stride + c8 + 4];
-        float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-        if constexpr (MODE == NOMIC_EPI_RESIDUAL) {
-          const uint4 rr = *(const uint4*)(ep.res + gm * ep.ldr + n0 + c8);
-          const uint32_t rw[4] = {rr.x, rr.y, rr.z, rr.w};
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            v[2 * e] += bf2f((uint16_t)(rw[e] & 0xffff));
-            v[2 * e + 1] += bf2f((uint16_t)(rw[e] >> 16));
-          }
-        }
-        *(uint4*)(ep.out + gm * ep.ldo + n0 + c8) = pack8(v);
-      }
-    } else if constexpr (MODE == NOMIC_EPI_SWIGLU) {
-      // block columns [up16 | gate16] x 8 (pack_upgate) -> output columns nt*128 + 0..127
-#pragma unroll
-      for (int it = 0; it < (128 * 128 / 8) / kThreads2; ++it) {
-        const int q = tid + it * kThreads2;
-        const int row = q >> 4, oc = (q & 15) * 8;
-        const long gm = mh + row;
-        if (gm >= ep.M) continue;
-        const int uc = 32 * (oc >> 4) + (oc & 15);
-        float o[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float up = E[row * kEpi2Stride + uc + e];
-          const float g = E[row * kEpi2Stride + uc + 16 + e];
-          o[e] = swiglu(up, g);
-        }
-        *(uint4*)(ep.out + gm * ep.ldo + (long)nt * 128 + oc) = pack8(o);
-      }
-    } else if constexpr (MODE == NOMIC_EPI_ROPE) {
-      // four 64-wide heads per block; NEOX rotation pairs (d, d + 32)
-#pragma unroll
-      for (int it = 0; it < (128 * 4 * 4) / kThreads2; ++it) {
-        const int q = tid + it * kThreads2;
-        const int row = q >> 4, head = (q >> 2) & 3, d0 = (q & 3) * 8;
-        const long gm = mh + row;
-        if (gm >= ep.M) continue;
-        const int cb = head * 64;
-        const long gcol = n0 + cb;
-        const int pc = d0 < 16 ? d0 : d0 + 16;  // pack_qkv layout
-        float x1[8], x2[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          x1[e] = E[row * kEpi2Stride + cb + pc + e];
-          x2[e] = E[row * kEpi2Stride + cb + pc + 16 + e];
-        }
-        if (gcol < ep.rope_cols) {
-          const float* cs = ep.rope + (long)ep.pos[gm] * 64 + d0 * 2;
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            const float c = cs[2 * e], s = cs[2 * e + 1];
-            const float a = x1[e], b = x2[e];
-            x1[e] = a * c - b * s;
-            x2[e] = b * c + a * s;
-          }
-        }
-        *(uint4*)(ep.out + gm * ep.ldo + gcol + d0) = pack8(x1);
-        *(uint4*)(ep.out + gm * ep.ldo + gcol + d0 + 32) = pack8(x2);
-      }
-    } else if constexpr (MODE == NOMIC_EPI_F32) {
-      float* outf = (float*)ep.out;
-#pragma unroll
-      for (int it = 0; it < (128 * 256 / 4) / kThreads2; ++it) {
-        const int q = tid + it * kThreads2;
-        const int row = q >> 6, c4 = (q & 63) * 4;
-        const long gm = mh + row;
-        if (gm >= ep.M) continue;
-        *(float4*)(outf + gm * ep.ldo + n0 + c4) = *(const float4*)&E[row * kEpi2Stride + c4];
-      }
-    }
+#include "gemm_epilogue128_body.hpp"  // the same text as k_gemm_nt's, on a 256-column image
   }
 }
 
@@ -871,29 +565,26 @@ int launch(const uint16_t* A, long lda, const uint16_t* W, long ldw, long M, int
   // the 256^2 kernel runs 1 block/CU with a serial prologue / epilogue per tile: it wins once there
   // are several waves of tiles.  From 1024 tiles: the qkv projection at 32768 tokens (1152 tiles)
   // measured 137.4 us on it against 144.5 us on the 128^2 kernel (round-3 trace); the SwiGLU GEMM
-  // has 3072.  The statistics epilogues exist in the 128^2 kernel only.
-  constexpr bool k256_ok = MODE <= NOMIC_EPI_F32;
+  // has 3072.
   const long tiles256 = fits ? (mpad / 256) * (N / 256) : 0;
   static const long min_tiles = [] {  // NOMIC_GEMM256_MIN_TILES (A/B knob)
     const char* e = getenv("NOMIC_GEMM256_MIN_TILES");
     return e && atol(e) > 0 ? atol(e) : 1024L;
   }();
-  if (k256_ok && fits && (var == 256 || (var == 0 && tiles256 >= min_tiles))) {
+  if (fits && (var == 256 || (var == 0 && tiles256 >= min_tiles))) {
     spl::allow_lds<k_gemm256<MODE>>(kLds2SplitBytes);
     const int mtiles = (int)(mpad / 256), ntiles = N / 256;
     ep.gn = band_width(ntiles, 4);
     ep.nsplit = split_tiles(tiles256);
     // a launch without half-tile blocks is what it was: same grid, same LDS size
-    if constexpr (k256_ok)
-      hipLaunchKernelGGL((k_gemm256<MODE>), dim3(mtiles * ntiles + ep.nsplit), dim3(kThreads2),
-                         ep.nsplit ? kLds2SplitBytes : kLds2Bytes, s, A, lda, W, ldw, K, mtiles, ntiles, ep);
+    hipLaunchKernelGGL((k_gemm256<MODE>), dim3(mtiles * ntiles + ep.nsplit), dim3(kThreads2),
+                       ep.nsplit ? kLds2SplitBytes : kLds2Bytes, s, A, lda, W, ldw, K, mtiles, ntiles, ep);
     return (int)hipGetLastError();
   }
   const int mtiles = (int)((M + BM - 1) / BM), ntiles = N / BN;
   ep.gn = band_width(ntiles, 8);
-  constexpr int lds = kLdsBytes + (needs_rowstats(MODE) ? BM * 8 : 0);
-  hipLaunchKernelGGL(k_gemm_nt<MODE>, dim3(mtiles * ntiles), dim3(kThreads), lds, s, A, lda, W, ldw, K, mtiles, ntiles,
-                     ep);
+  hipLaunchKernelGGL(k_gemm_nt<MODE>, dim3(mtiles * ntiles), dim3(kThreads), kLdsBytes, s, A, lda, W, ldw, K, mtiles,
+                     ntiles, ep);
   return (int)hipGetLastError();
 }
 
@@ -917,16 +608,12 @@ extern "C" long nomic_gemm256_grid(long M, int N) {
   return T + split_tiles(T);
 }
 
-extern "C" int nomic_gemm_ln(int mode, const void* A, long lda, const void* W, long ldw, long M, int N, int K,
-                             void* out, long ldo, const void* res, long ldr, const float* rope, const int32_t* pos,
-                             int rope_cols, const float* part_in, int nparts, float eps, const float* c1,
-                             const float* c2, const void* ln_g, const void* ln_b, float* part, hipStream_t s) {
-  EpiArgs ep{(uint16_t*)out, ldo, (const uint16_t*)res, ldr, rope, pos, rope_cols, M, 1, (const float2*)part_in,
-             nparts, eps, c1, c2, (const uint16_t*)ln_g, (const uint16_t*)ln_b, (float2*)part};
-  // operands each mode reads must be there (a fold / stats launch without them would fault)
-  if ((needs_rowstats(mode) && (!part_in || nparts < 1 || nparts > 8)) || (is_fold(mode) && (!c1 || !c2)) ||
-      (is_stats(mode) && (!part || !res || N % BN)) || (mode == NOMIC_EPI_RES_LN_STATS && (!ln_g || !ln_b)) ||
-      (mode == NOMIC_EPI_RESIDUAL && !res) || (is_rope(mode) && (!rope || !pos)))
+extern "C" int nomic_gemm(int mode, const void* A, long lda, const void* W, long ldw, long M, int N, int K, void* out,
+                          long ldo, const void* res, long ldr, const float* rope, const int32_t* pos, int rope_cols,
+                          hipStream_t s) {
+  EpiArgs ep{(uint16_t*)out, ldo, (const uint16_t*)res, ldr, rope, pos, rope_cols, M, 1, 0};
+  // operands each mode reads must be there (a launch without them would fault)
+  if ((mode == NOMIC_EPI_RESIDUAL && !res) || (mode == NOMIC_EPI_ROPE && (!rope || !pos)))
     return (int)hipErrorInvalidValue;
   const auto* a = (const uint16_t*)A;
   const auto* w = (const uint16_t*)W;
@@ -936,44 +623,6 @@ extern "C" int nomic_gemm_ln(int mode, const void* A, long lda, const void* W, l
     case NOMIC_EPI_SWIGLU: return launch<NOMIC_EPI_SWIGLU>(a, lda, w, ldw, M, N, K, ep, s);
     case NOMIC_EPI_ROPE: return launch<NOMIC_EPI_ROPE>(a, lda, w, ldw, M, N, K, ep, s);
     case NOMIC_EPI_F32: return launch<NOMIC_EPI_F32>(a, lda, w, ldw, M, N, K, ep, s);
-    case NOMIC_EPI_ROPE_FOLD: return launch<NOMIC_EPI_ROPE_FOLD>(a, lda, w, ldw, M, N, K, ep, s);
-    case NOMIC_EPI_SWIGLU_FOLD: return launch<NOMIC_EPI_SWIGLU_FOLD>(a, lda, w, ldw, M, N, K, ep, s);
-    case NOMIC_EPI_RES_STATS: return launch<NOMIC_EPI_RES_STATS>(a, lda, w, ldw, M, N, K, ep, s);
-    case NOMIC_EPI_RES_LN_STATS: return launch<NOMIC_EPI_RES_LN_STATS>(a, lda, w, ldw, M, N, K, ep, s);
     default: return (int)hipErrorInvalidValue;
   }
-}
-
-extern "C" int nomic_gemm(int mode, const void* A, long lda, const void* W, long ldw, long M, int N, int K, void* out,
-                          long ldo, const void* res, long ldr, const float* rope, const int32_t* pos, int rope_cols,
-                          hipStream_t s) {
-  if (mode > NOMIC_EPI_F32) return (int)hipErrorInvalidValue;  // the LN modes go through nomic_gemm_ln
-  return nomic_gemm_ln(mode, A, lda, W, ldw, M, N, K, out, ldo, res, ldr, rope, pos, rope_cols, nullptr, 0, 0.f,
-                       nullptr, nullptr, nullptr, nullptr, nullptr, s);
-}
-
-namespace {
-// one thread per row: Chan's combination of equal-size (128-column) partials
-__global__ void k_row_stats(const float2* __restrict__ part, int np, long M, float eps, float2* __restrict__ st) {
-  const long m = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (m >= M) return;
-  const float2* p = part + m * np;
-  float mean = 0.f;
-  for (int i = 0; i < np; ++i) mean += p[i].x;
-  mean /= (float)np;
-  float m2 = 0.f;
-  for (int i = 0; i < np; ++i) {
-    const float d = p[i].x - mean;
-    m2 += p[i].y + (float)BN * d * d;
-  }
-  const float var = m2 / ((float)BN * (float)np);
-  st[m] = make_float2(mean, rsqrtf(var + eps));
-}
-}  // namespace
-
-extern "C" int nomic_row_stats(const float* part, int nparts, long M, float eps, float* st, hipStream_t s) {
-  if (nparts <= 0 || M <= 0 || !part || !st) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_row_stats, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, (const float2*)part, nparts, M,
-                     eps, (float2*)st);
-  return (int)hipGetLastError();
 }

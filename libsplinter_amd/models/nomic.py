@@ -33,8 +33,6 @@ from ..utils.tracing import trace_range
 from .gguf import DEVICE_DEQUANT, GGUFFile, GGUFWriter, dequant_host
 
 EPI_STORE, EPI_RESIDUAL, EPI_SWIGLU, EPI_ROPE, EPI_F32 = 0, 1, 2, 3, 4
-# post-LayerNorm folded into the neighbouring GEMMs (csrc/include/nomic_api.h)
-EPI_ROPE_FOLD, EPI_SWIGLU_FOLD, EPI_RES_STATS, EPI_RES_LN_STATS = 5, 6, 7, 8
 
 
 @dataclass
@@ -70,16 +68,11 @@ def _lib():
         P, c_long, c_int, c_float = ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_float
         L.nomic_gemm.argtypes = [c_int, P, c_long, P, c_long, c_long, c_int, c_int, P, c_long, P, c_long, P, P, c_int, P]
         L.nomic_gemm.restype = c_int
-        L.nomic_gemm_ln.argtypes = [c_int, P, c_long, P, c_long, c_long, c_int, c_int, P, c_long, P, c_long, P, P,
-                                    c_int, P, c_int, c_float, P, P, P, P, P, P]
-        L.nomic_gemm_ln.restype = c_int
         L.nomic_gemm_res_ln.argtypes = [P, c_long, P, c_long, c_long, c_int, c_int, P, c_long, P, P, c_float, P,
                                         c_long, P]
         L.nomic_gemm_res_ln.restype = c_int
         L.nomic_gemm_res_ln_set_variant.argtypes = [c_int]
         L.nomic_gemm_res_ln_set_variant.restype = c_int
-        L.nomic_row_stats.argtypes = [P, c_int, c_long, c_float, P, P]
-        L.nomic_row_stats.restype = c_int
         L.nomic_gemm_set_variant.argtypes = [c_int]
         L.nomic_gemm_set_variant.restype = c_int
         L.nomic_gemm384_set_bk.argtypes = [c_int]
@@ -194,20 +187,8 @@ def pack_qkv(w: torch.Tensor) -> torch.Tensor:
     return w.reshape(n // 64, 64, d)[:, _QKV_PERM.to(w.device)].reshape(n, d)
 
 
-def fold_ln(w: torch.Tensor, g: torch.Tensor, b: torch.Tensor):
-    """LayerNorm folded into the linear that consumes it: LN(h) w^T = rstd (h w'^T - mean c1) + c2
-    with w' = w diag(g) (bf16), c1 = w' 1 and c2 = w b (fp32; c1 from the ROUNDED w', so the mean
-    term cancels exactly what the GEMM accumulates).  w [N, K] in kernel (packed) row order."""
-    wf = (w.float() * g.float()[None, :]).to(torch.bfloat16).contiguous()
-    c1 = wf.float().sum(1).contiguous()
-    c2 = (w.float() @ b.float()).contiguous()
-    return wf, c1, c2
-
-
 class NomicWeights:
-    """Device-resident bf16 weights in kernel layout.  The LN-folded copies that only the "folded"
-    schedule reads (``wqkv_f`` folds the previous layer's output LN, ``wupgate_f`` this layer's
-    attention-output LN) are built by the first ``folded()`` call."""
+    """Device-resident bf16 weights in kernel layout."""
 
     def __init__(self, cfg: NomicConfig, tensors: Dict[str, torch.Tensor], device="cuda"):
         self.cfg = cfg
@@ -224,18 +205,6 @@ class NomicWeights:
                 "wdown": bf(t["wdown"]),
                 "ln1_g": bf(t["ln1_g"]), "ln1_b": bf(t["ln1_b"]), "ln2_g": bf(t["ln2_g"]), "ln2_b": bf(t["ln2_b"]),
             })
-
-    def folded(self):
-        """The layer dicts with the LN-folded copies and their fp32 constants added (built once, about
-        13 MB per layer at the shipped shape)."""
-        for i, lw in enumerate(self.layers):
-            if "wupgate_f" in lw:
-                continue
-            lw["wupgate_f"], lw["ug_c1"], lw["ug_c2"] = fold_ln(lw["wupgate"], lw["ln1_g"], lw["ln1_b"])
-            if i > 0:
-                prev = self.layers[i - 1]
-                lw["wqkv_f"], lw["qkv_c1"], lw["qkv_c2"] = fold_ln(lw["wqkv"], prev["ln2_g"], prev["ln2_b"])
-        return self.layers
 
     @classmethod
     def from_numpy(cls, cfg, weights: Dict[str, np.ndarray], device="cuda"):
@@ -385,25 +354,20 @@ class NomicEncoder:
         tab = np.stack([np.cos(ang), np.sin(ang)], axis=-1).astype(np.float32)
         self.rope = torch.from_numpy(tab.reshape(npos, -1)).cuda()
         self._ws_tokens, self._ws_schedule = 0, None
-        self.h = self.h2 = self.part1 = self.part2 = None
+        self.h = None
         self._scale = 1.0 / math.sqrt(cfg.head_dim)
         self._ensure(max_tokens)
 
     def _ensure(self, T_pad: int):
         """Workspaces of at least T_pad rows for the schedule in force: x, attn, qkv and ffn for every
-        schedule, h for "split" and "folded", h2 and the row-statistics partials for "folded" only,
-        so the default schedule does not pay for the opt-in ones."""
+        schedule, h for "split" only, so the default schedule does not pay for the opt-in one."""
         if T_pad <= self._ws_tokens and self._ws_schedule == self.schedule:
             return
         cfg = self.cfg
-        bf, f32 = torch.bfloat16, torch.float32
+        bf = torch.bfloat16
         want = {"x": (cfg.d, bf), "attn": (cfg.d, bf), "qkv": (3 * cfg.d, bf), "ffn": (cfg.ffn, bf)}
-        if self.schedule in ("split", "folded"):
+        if self.schedule == "split":
             want["h"] = (cfg.d, bf)
-        if self.schedule == "folded":
-            want["h2"] = (cfg.d, bf)
-            want["part1"] = (2 * (cfg.d // 128), f32)  # (mean, M2) per 128 columns of h1
-            want["part2"] = (2 * (cfg.d // 128), f32)  # ... of h2
         rows = max(T_pad, self._ws_tokens)
         for name, (cols, dtype) in want.items():
             t = getattr(self, name, None)
@@ -418,16 +382,6 @@ class NomicEncoder:
                                N_, K, out.data_ptr(), out.stride(0), res.data_ptr() if res is not None else None,
                                res.stride(0) if res is not None else 0, self.rope.data_ptr(),
                                pos.data_ptr() if pos is not None else None, 2 * self.cfg.d, s), "gemm")
-
-    def _gemm_ln(self, mode, A, W, M, out, s, res=None, pos=None, pin=None, c1=None, c2=None, ln=None, part=None):
-        N_, K = W.shape
-        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-        _chk(self.L.nomic_gemm_ln(mode, A.data_ptr(), A.stride(0), W.data_ptr(), W.stride(0), M, N_, K,
-                                  out.data_ptr(), out.stride(0), ptr(res), res.stride(0) if res is not None else 0,
-                                  self.rope.data_ptr(), ptr(pos), 2 * self.cfg.d, ptr(pin),
-                                  pin.shape[1] // 2 if pin is not None else 0, self.cfg.eps, ptr(c1), ptr(c2),
-                                  ptr(ln[0]) if ln else None, ptr(ln[1]) if ln else None, ptr(part), s),
-             f"gemm_ln({mode})")
 
     def _res_ln(self, A, W, M, x, g, beta, s):
         """x[:M] = LN(A W^T + x) * g + beta in place (row-complete MFMA kernel, gemm_rln.hip)."""
@@ -458,11 +412,9 @@ class NomicEncoder:
     # Schedules of the post-LN layers (K15 / K16-down), all on hand-written kernels:
     #   "fused"  (default) residual GEMM + residual add + LayerNorm in one row-complete kernel
     #            (csrc/hip/gemm_rln.hip): x = LN(a W^T + x) in place, no separate LN pass;
-    #   "split"  the residual GEMM (EPI_RESIDUAL) then the LayerNorm kernel (round-1 schedule);
-    #   "folded" every post-LN folded into the neighbouring GEMMs (measured slower,
-    #            profiles/r2_encoder_ln_fold.md).
-    # NOMIC_SCHEDULE overrides; NOMIC_LN_FOLD=1 is the old spelling of "folded".
-    schedule = os.environ.get("NOMIC_SCHEDULE", "folded" if os.environ.get("NOMIC_LN_FOLD", "0") != "0" else "fused")
+    #   "split"  the residual GEMM (EPI_RESIDUAL) then the LayerNorm kernel (round-1 schedule).
+    # NOMIC_SCHEDULE overrides.
+    schedule = os.environ.get("NOMIC_SCHEDULE", "fused")
 
     # NOMIC_SPLIT=N (N > 1): the batch's documents in N groups, each group's layer chain on its own
     # stream, issued layer by layer in turn, so one group's kernels fill the CUs another group's
@@ -471,8 +423,6 @@ class NomicEncoder:
 
     def hidden(self, b: Batch) -> torch.Tensor:
         """Final-layer hidden states [T, 768] (bf16) for a packed batch."""
-        if self.schedule == "folded":
-            return self._hidden_folded(b)
         if self.schedule == "split":
             return self._hidden_unfused(b)
         if self.schedule != "fused":
@@ -516,37 +466,6 @@ class NomicEncoder:
         for st in streams:
             cur.wait_stream(st)
         return self.x[: b.T]
-
-    def _hidden_folded(self, b: Batch) -> torch.Tensor:
-        """The forward with every post-LN folded into the GEMMs around it (K15): the residual GEMMs
-        write raw sums h1 / h2 plus 128-column partial row statistics; the next projection combines
-        them into (mean, rstd) per row in its prologue and runs on raw h against LN-folded weights,
-        and the next residual GEMM normalises its residual operand on the fly.  One LayerNorm pass
-        per forward (the final one, for pooling) instead of two per layer."""
-        s = self._begin(b)
-        T = b.T
-        x, h1, h2, attn, qkv, ffn = self.x, self.h, self.h2, self.attn, self.qkv, self.ffn
-        p1, p2 = self.part1, self.part2
-        self._embed_ln(b, x, s)
-        prev = None
-        for lw in self.w.folded():
-            if prev is None:
-                self._gemm(EPI_ROPE, x, lw["wqkv"], T, qkv, s, pos=b.pos)
-            else:
-                self._gemm_ln(EPI_ROPE_FOLD, h2, lw["wqkv_f"], T, qkv, s, pos=b.pos, pin=p2, c1=lw["qkv_c1"],
-                              c2=lw["qkv_c2"])
-            self._attention(b, qkv, attn, s)
-            if prev is None:
-                self._gemm_ln(EPI_RES_STATS, attn, lw["wo"], T, h1, s, res=x, part=p1)
-            else:
-                self._gemm_ln(EPI_RES_LN_STATS, attn, lw["wo"], T, h1, s, res=h2, pin=p2,
-                              ln=(prev["ln2_g"], prev["ln2_b"]), part=p1)
-            self._gemm_ln(EPI_SWIGLU_FOLD, h1, lw["wupgate_f"], T, ffn, s, pin=p1, c1=lw["ug_c1"], c2=lw["ug_c2"])
-            self._gemm_ln(EPI_RES_LN_STATS, ffn, lw["wdown"], T, h2, s, res=h1, pin=p1,
-                          ln=(lw["ln1_g"], lw["ln1_b"]), part=p2)
-            prev = lw
-        self._layernorm(h2, T, prev["ln2_g"], prev["ln2_b"], x, s, "ln_final")
-        return x[:T]
 
     def _hidden_unfused(self, b: Batch) -> torch.Tensor:
         """Split schedule: the residual GEMM, then a LayerNorm kernel (NOMIC_SCHEDULE=split)."""

@@ -127,86 +127,78 @@ def test_gemm256_swiglu_epilogue(L0):
     assert (out[M:].float() == 7.0).all()  # rows past M are never written
 
 
-def test_gemm_layernorm_fold_modes(L):
-    """Post-LN folded into the GEMMs (nomic_api.h modes 5-8) vs fp32 torch: residual sums with
-    128-column partial statistics -> (mean, rstd) per row; the residual normalised on the fly;
-    SwiGLU and RoPE projections of LN(h) computed from raw h against LN-folded weights."""
+@pytest.mark.parametrize("mode,res,rope,pos", [(5, 1, 1, 1), (6, 1, 1, 1), (7, 1, 1, 1), (8, 1, 1, 1), (1, 0, 1, 1),
+                                               (3, 1, 0, 1), (3, 1, 1, 0), (3, 1, 0, 0)])
+def test_gemm_refuses_retired_modes_and_missing_operands(L, mode, res, rope, pos):
+    """nomic_gemm returns an error and launches nothing (a sentinel-filled output stays as it was)
+    for a mode above NOMIC_EPI_F32 (5-8 were the LayerNorm-fold epilogues), for RESIDUAL without
+    `res` and for ROPE without `rope` or `pos`."""
     import torch
-    from libsplinter_amd.models.nomic import (NomicConfig, NomicReference, _chk, _stream, fold_ln, pack_qkv,
-                                              pack_upgate)
-    F_ = torch.nn.functional
-    torch.manual_seed(3)
-    M, K, F, eps = 300, 768, 3072, 1e-12
-    Mp = 384
-    nul = None
+    from libsplinter_amd.models.nomic import _stream
+    M, N, K = 128, 256, 64
+    A = torch.randn(M, K, device="cuda").bfloat16()
+    W = torch.randn(N, K, device="cuda").bfloat16()
+    R = torch.randn(M, N, device="cuda").bfloat16()
+    tab = torch.ones(64, 64, device="cuda")
+    p = torch.zeros(M, device="cuda", dtype=torch.int32)
+    out = torch.full((M, N), 7.0, device="cuda", dtype=torch.bfloat16)
+    rc = L.nomic_gemm(mode, A.data_ptr(), K, W.data_ptr(), K, M, N, K, out.data_ptr(), N,
+                      R.data_ptr() if res else None, N if res else 0, tab.data_ptr() if rope else None,
+                      p.data_ptr() if pos else None, 128, _stream())
+    torch.cuda.synchronize()
+    assert rc != 0
+    assert (out.float() == 7.0).all(), "a refused call must not launch"
 
-    def gemm_ln(mode, A, W, out, res=None, pos=None, tab=None, pin=None, c1=None, c2=None, g=None, b=None,
-                part=None):
-        p = lambda t: t.data_ptr() if t is not None else nul  # noqa: E731
-        _chk(L.nomic_gemm_ln(mode, A.data_ptr(), A.stride(0), W.data_ptr(), W.stride(0), M, W.shape[0], W.shape[1],
-                             out.data_ptr(), out.stride(0), p(res), res.stride(0) if res is not None else 0, p(tab),
-                             p(pos), 2 * K, p(pin), K // 128 if pin is not None else 0, eps, p(c1), p(c2), p(g), p(b),
-                             p(part), _stream()), f"mode {mode}")
 
-    def partials(t):  # (mean, M2) per 128 columns, as a stats-mode producer writes them
-        v = t.float().reshape(t.shape[0], -1, 128)
-        mu = v.mean(2)
-        return torch.stack([mu, ((v - mu[..., None]) ** 2).sum(2)], 2).reshape(t.shape[0], -1).contiguous()
+@pytest.fixture(scope="module")
+def epi_inputs():
+    """Seeded operands of the kernel-agreement test, made once: M = 300 rows in 512-row buffers."""
+    import torch
+    torch.manual_seed(7)
+    ang = np.arange(2048)[:, None] * (1000.0 ** (-np.arange(0, 64, 2) / 64))[None, :]
+    return {"A": torch.randn(512, 192, device="cuda").bfloat16(),
+            "W": (torch.randn(512, 192, device="cuda") * 0.05).bfloat16(),
+            "R": torch.randn(512, 512, device="cuda").bfloat16(),
+            "pos": torch.randint(0, 2048, (512,), device="cuda", dtype=torch.int32),
+            "tab": torch.from_numpy(np.stack([np.cos(ang), np.sin(ang)], -1).astype(np.float32).reshape(2048, -1)).cuda()}
 
-    # raw residual stream with a per-row offset (the fold must cancel the mean exactly)
-    h = (torch.randn(Mp, K, device="cuda") * 1.5 + torch.randn(Mp, 1, device="cuda") * 2).bfloat16()
-    g = (1 + 0.3 * torch.randn(K, device="cuda")).bfloat16()
-    bb = (0.1 * torch.randn(K, device="cuda")).bfloat16()
-    hf = h[:M].float()
-    xln = F_.layer_norm(hf, (K,), g.float(), bb.float(), eps)
-    ph = partials(h)
 
-    # 7: out = A W^T + R, partial stats -> row_stats
-    A = torch.randn(Mp, K, device="cuda").bfloat16()
-    W = (torch.randn(K, K, device="cuda") * 0.03).bfloat16()
-    out = torch.zeros(Mp, K, device="cuda", dtype=torch.bfloat16)
-    part = torch.zeros(Mp, 2 * (K // 128), device="cuda")
-    gemm_ln(7, A, W, out, res=h, part=part)
-    ref = A[:M].float() @ W.float().T + hf
-    assert _rel(out[:M].float(), ref) < 5e-3
-    assert (out[M:] == 0).all()
-    st_got = torch.zeros(Mp, 2, device="cuda")
-    _chk(L.nomic_row_stats(part.data_ptr(), K // 128, M, eps, st_got.data_ptr(), _stream()), "row_stats")
-    o = out[:M].float()
-    torch.testing.assert_close(st_got[:M, 0], o.mean(1), rtol=1e-4, atol=1e-4)
-    torch.testing.assert_close(st_got[:M, 1], torch.rsqrt(o.var(1, unbiased=False) + eps), rtol=1e-3, atol=1e-4)
-
-    # 8: out = A W^T + LN(h) with h's statistics
-    gemm_ln(8, A, W, out, res=h, pin=ph, g=g, b=bb, part=part)
-    assert _rel(out[:M].float(), A[:M].float() @ W.float().T + xln) < 5e-3
-
-    # 6: SwiGLU of LN(h) from raw h and folded weights
-    up = (torch.randn(F, K, device="cuda") * 0.03).bfloat16()
-    gate = (torch.randn(F, K, device="cuda") * 0.03).bfloat16()
-    wf, c1, c2 = fold_ln(pack_upgate(up, gate), g, bb)
-    ffn = torch.empty(Mp, F, device="cuda", dtype=torch.bfloat16)
-    gemm_ln(6, h, wf, ffn, pin=ph, c1=c1, c2=c2)
-    ref = (xln @ up.float().T) * F_.silu(xln @ gate.float().T)
-    assert _rel(ffn[:M].float(), ref) < 1.5e-2
-
-    # 5: RoPE'd qkv of LN(h)
-    cfg = NomicConfig()
-    wqkv = (torch.randn(3 * K, K, device="cuda") * 0.03).bfloat16()
-    pos = torch.randint(0, 2000, (Mp,), device="cuda", dtype=torch.int32)
-    inv = cfg.rope_base ** (-np.arange(0, 64, 2) / 64)
-    ang = np.arange(8192)[:, None] * inv[None, :]
-    tab = torch.from_numpy(np.stack([np.cos(ang), np.sin(ang)], -1).astype(np.float32).reshape(8192, -1)).cuda()
-    wf, c1, c2 = fold_ln(pack_qkv(wqkv), g, bb)
-    qkv = torch.empty(Mp, 3 * K, device="cuda", dtype=torch.bfloat16)
-    gemm_ln(5, h, wf, qkv, pos=pos, tab=tab, pin=ph, c1=c1, c2=c2)
-    raw = xln @ wqkv.float().T
-    rm = NomicReference(cfg, {}, "cuda")
-    q = rm.rope(raw[:, :K].reshape(M, 12, 64), pos[:M].long()).reshape(M, K)
-    k = rm.rope(raw[:, K:2 * K].reshape(M, 12, 64), pos[:M].long()).reshape(M, K)
-    assert _rel(qkv[:M].float(), torch.cat([q, k, raw[:, 2 * K:]], 1)) < 1.5e-2
-    # a fold mode without its operands is refused, never launched
-    assert L.nomic_gemm_ln(6, h.data_ptr(), K, wf.data_ptr(), K, M, 3 * K, K, qkv.data_ptr(), 3 * K, None, 0, None,
-                           None, 0, None, 0, eps, None, None, None, None, None, _stream()) != 0
+@pytest.mark.parametrize("K", [64, 128, 192])
+@pytest.mark.parametrize("mode", [0, 1, 2, 3, 4])
+def test_gemm128_and_gemm256_agree_bit_for_bit(L0, epi_inputs, mode, K):
+    """Both kernels accumulate K in the same 32-wide MFMA order and share one epilogue, so every mode
+    writes the same bits from the 128^2 kernel and from the 256^2 kernel with its tail split off and
+    on.  M = 300 is a partial last row tile for both (with the split on, all four 256^2 tiles run as
+    half-tile blocks, one of them wholly past M); K = 64 / 128 / 192 is one K-tile, the peeled pair
+    and the steady loop; RoPE stops inside a 256-column tile (5 of 8 heads).  Rows >= M of the
+    sentinel-filled output are never written."""
+    import torch
+    from libsplinter_amd.models.nomic import _chk, _stream
+    M, N = 300, 512
+    e = epi_inputs
+    A, W = e["A"][:, :K], e["W"][:, :K]  # row stride 192
+    ocols, dtype = (N // 2 if mode == 2 else N), (torch.float32 if mode == 4 else torch.bfloat16)
+    outs = []
+    pv, ps = L0.nomic_gemm_set_variant(0), L0.nomic_gemm_set_tail_split(1)
+    try:
+        for variant, split, grid in ((128, 1, None), (256, 0, 4), (256, 1, 8)):
+            L0.nomic_gemm_set_variant(variant)
+            L0.nomic_gemm_set_tail_split(split)
+            if grid:
+                assert L0.nomic_gemm256_grid(M, N) == grid
+            out = torch.full((512, ocols), 7.0, device="cuda", dtype=dtype)
+            _chk(L0.nomic_gemm(mode, A.data_ptr(), A.stride(0), W.data_ptr(), W.stride(0), M, N, K, out.data_ptr(),
+                               ocols, e["R"].data_ptr(), N, e["tab"].data_ptr(), e["pos"].data_ptr(), 320, _stream()),
+                 f"gemm{variant}")
+            outs.append(out)
+        torch.cuda.synchronize()
+    finally:
+        L0.nomic_gemm_set_variant(pv)
+        L0.nomic_gemm_set_tail_split(ps)
+    assert (outs[0][M:] == 7.0).all(), "rows past M must not be written"
+    assert (outs[0][:M] != 7.0).any(dim=1).all(), "every row below M is written"
+    assert torch.equal(outs[0], outs[1]), "128^2 vs 256^2, tail split off"
+    assert torch.equal(outs[0], outs[2]), "128^2 vs 256^2, tail split on"
 
 
 @pytest.mark.parametrize("variant", [13, 6])
@@ -311,7 +303,7 @@ def test_gemm_residual_layernorm_row_complete(L0, M, K, rln_variant):
                                 b.data_ptr(), 1e-12, X.data_ptr(), N, _stream()) != 0
 
 
-@pytest.mark.parametrize("schedule", ["fused", "split", "folded"])
+@pytest.mark.parametrize("schedule", ["fused", "split"])
 def test_encoder_matches_fp32_reference(schedule):
     import torch
     from libsplinter_amd.models.nomic import (Batch, NomicConfig, NomicEncoder, NomicReference, NomicWeights,
@@ -330,27 +322,32 @@ def test_encoder_matches_fp32_reference(schedule):
     assert _rel(got, ref) < 3e-2
 
 
-def test_folded_weights_and_workspaces_exist_only_after_a_folded_forward():
-    """The default schedule neither builds the LN-folded weight copies nor allocates the workspaces
-    only the "folded" schedule reads; the first folded forward makes them, the second reuses them."""
+def test_split_workspace_exists_only_after_a_split_forward():
+    """The default schedule does not allocate `h`, the workspace only the "split" schedule reads;
+    the first split forward makes it, the second reuses it."""
     from libsplinter_amd.models.nomic import Batch, NomicConfig, NomicEncoder, NomicWeights, random_weights
     cfg = NomicConfig(layers=2)
-    w = NomicWeights.from_numpy(cfg, random_weights(cfg, seed=3))
-    enc = NomicEncoder(w, max_tokens=256)
+    enc = NomicEncoder(NomicWeights.from_numpy(cfg, random_weights(cfg, seed=3)), max_tokens=256)
     assert enc.schedule == "fused"
     b = Batch([[1, 2, 3, 4, 5], list(range(7, 47))])
     enc.embed(b)
-    folded_keys, folded_ws = ("wupgate_f", "wqkv_f"), ("h2", "part1", "part2")
-    assert not any(k in lw for lw in w.layers for k in folded_keys)
-    assert all(getattr(enc, n, None) is None for n in folded_ws)
+    assert getattr(enc, "h", None) is None
+    enc.schedule = "split"
+    enc.embed(b)
+    first = enc.h
+    assert first.shape[0] >= b.T_pad
+    enc.embed(b)
+    assert enc.h is first
+
+
+def test_folded_schedule_is_refused():
+    """The LayerNorm-fold schedule was removed: asking for it is an unknown-schedule error."""
+    from libsplinter_amd.models.nomic import Batch, NomicConfig, NomicEncoder, NomicWeights, random_weights
+    cfg = NomicConfig(layers=1)
+    enc = NomicEncoder(NomicWeights.from_numpy(cfg, random_weights(cfg, seed=3)), max_tokens=128)
     enc.schedule = "folded"
-    enc.embed(b)
-    assert all("wupgate_f" in lw for lw in w.layers) and "wqkv_f" in w.layers[1]
-    assert all(getattr(enc, n).shape[0] >= b.T_pad for n in folded_ws + ("h",))
-    first = [lw[k] for lw in w.layers for k in folded_keys if k in lw] + [getattr(enc, n) for n in folded_ws]
-    enc.embed(b)
-    again = [lw[k] for lw in w.layers for k in folded_keys if k in lw] + [getattr(enc, n) for n in folded_ws]
-    assert len(first) == 3 + 3 and all(x is y for x, y in zip(first, again))
+    with pytest.raises(ValueError, match="unknown encoder schedule"):
+        enc.hidden(Batch([[1, 2, 3]]))
 
 
 def test_gguf_roundtrip_device_dequant(tmp_path):
