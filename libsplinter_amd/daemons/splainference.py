@@ -434,7 +434,13 @@ def main(argv=None) -> int:
         q = "q4" if a.quant == "q4" and device != "cpu" else "bf16"
         model, tok = CausalLM.random(cfg, device=device, quant=q), ByteTokenizer()
     else:
-        model, tok = CausalLM.from_gguf(a.gguf, device=device, quant=a.quant)
+        try:
+            model, tok = CausalLM.from_gguf(a.gguf, device=device, quant=a.quant)
+        except ValueError as e:  # an architecture or rope layout the decoder does not compute: refuse to serve
+            print(f"Error: cannot serve `{a.gguf}`: {e}", file=sys.stderr)
+            store.shard_release(SHARD_ID)
+            store.close()
+            return 1
         if a.n_ctx > 0:
             model.cfg.n_ctx = min(a.n_ctx, model.cos.shape[0])
     print(f"[Startup]: context window = {model.cfg.n_ctx} tokens, {model.quant} weights.", flush=True)

@@ -7,7 +7,11 @@ the MI355X replacement, demo-grade as SURVEY §2.1 N8 scopes it:
 
 * weights: GGUF arch "llama" (token_embd, blk.N.{attn_norm, attn_q, attn_k,
   attn_v, attn_output, ffn_norm, ffn_gate, ffn_up, ffn_down}, output_norm,
-  output) dequantised on the device, or random init (``DecoderConfig``);
+  output) dequantised on the device, or random init (``DecoderConfig``); arch "qwen2" adds
+  blk.N.attn_{q,k,v}.bias, arch "qwen3" blk.N.attn_{q,k}_norm.weight and a head dim of its own
+  (attention.key_length); their NeoX rotation becomes the adjacent-pair one by a row permutation at load,
+  and bias + q/k norm + RoPE (+ cache append) are one fused launch (``csrc/hip/decoder_arch.hip``); any
+  other architecture is refused (``config_from_gguf``);
 * every projection (q|k|v fused, o + residual, gate|up + SwiGLU, down +
   residual, LM head) runs on the gfx950 MFMA GEMM (``nomic_gemm``) with its
   fused epilogues; RMSNorm and RoPE (llama "normal" adjacent-pair rotation, as
@@ -48,10 +52,35 @@ class DecoderConfig:
     eps: float = 1e-5
     rope_base: float = 10000.0
     n_ctx: int = 2048
+    arch: str = "llama"       # general.architecture: one of SUPPORTED_ARCHS
+    qkv_bias: bool = False    # blk.N.attn_{q,k,v}.bias (qwen2)
+    qk_norm: bool = False     # blk.N.attn_{q,k}_norm.weight, a per-head RMSNorm ahead of the rotation (qwen3)
+    key_length: Optional[int] = None  # {arch}.attention.key_length: the head dim where heads * head_dim != d
+    rope_scale: float = 1.0   # rope.scaling.factor of type "linear": positions are divided by it
 
     @property
     def head_dim(self) -> int:
-        return self.d // self.heads
+        return self.key_length or self.d // self.heads
+
+    @property
+    def q_dim(self) -> int:
+        """Width of the q columns, of the attention output and of the o-projection's K (d unless key_length)."""
+        return self.heads * self.head_dim
+
+
+# general.architecture values CausalLM computes (mistral files say "llama"); qwen2 / qwen3 rotate the halves
+# of a head against each other (NeoX), which the loader turns into adjacent pairs by permuting rows
+SUPPORTED_ARCHS = ("llama", "qwen2", "qwen3")
+NEOX_ARCHS = ("qwen2", "qwen3")
+
+
+def neox_rows_to_pairs(t: torch.Tensor, hd: int) -> torch.Tensor:
+    """Rows of t grouped in heads of hd: new row 2j of a head is old row j, new row 2j + 1 old row j + hd/2.
+    Applied to attn_q / attn_k weights, their biases and the per-head norm weights, it makes the adjacent-pair
+    rotation of the permuted head the NeoX rotation of the original one; q . k and the RMS over a head do not
+    change under a permutation applied to both."""
+    r = t.reshape(-1, 2, hd // 2, *t.shape[1:])
+    return r.transpose(1, 2).reshape(t.shape).contiguous()
 
 
 class ByteTokenizer:
@@ -84,14 +113,23 @@ def random_decoder_weights(cfg: DecoderConfig, seed: int = 0, std: float = 0.02)
     for i in range(cfg.layers):
         p = f"blk.{i}."
         w[p + "attn_norm.weight"] = np.ones(cfg.d, np.float32)
-        w[p + "attn_q.weight"] = f(cfg.d, cfg.d)
+        w[p + "attn_q.weight"] = f(cfg.q_dim, cfg.d)
         w[p + "attn_k.weight"] = f(kvd, cfg.d)
         w[p + "attn_v.weight"] = f(kvd, cfg.d)
-        w[p + "attn_output.weight"] = f(cfg.d, cfg.d)
+        w[p + "attn_output.weight"] = f(cfg.d, cfg.q_dim)
         w[p + "ffn_norm.weight"] = np.ones(cfg.d, np.float32)
         w[p + "ffn_gate.weight"] = f(cfg.ffn, cfg.d)
         w[p + "ffn_up.weight"] = f(cfg.ffn, cfg.d)
         w[p + "ffn_down.weight"] = f(cfg.d, cfg.ffn)
+    # the extras are drawn after every matrix, so a config without them keeps its weights
+    for i in range(cfg.layers):
+        p = f"blk.{i}."
+        if cfg.qkv_bias:
+            for n, rows in (("q", cfg.q_dim), ("k", kvd), ("v", kvd)):
+                w[p + f"attn_{n}.bias"] = (rng.standard_normal(rows) * 0.5).astype(np.float32)
+        if cfg.qk_norm:
+            for n in ("q", "k"):
+                w[p + f"attn_{n}_norm.weight"] = (1.0 + 0.1 * rng.standard_normal(cfg.head_dim)).astype(np.float32)
     return w
 
 
@@ -104,15 +142,38 @@ def gguf_quant_kind(g) -> str:
 
 
 def config_from_gguf(g) -> DecoderConfig:
+    """ValueError for an architecture CausalLM does not compute, for partial rotary and for a rope scaling type
+    other than none / linear / yarn: such a file would load and write wrong text."""
     a = g.arch() or "llama"
+    if a not in SUPPORTED_ARCHS:
+        raise ValueError(f"architecture {a!r} is not supported (supported: {', '.join(SUPPORTED_ARCHS)})")
     get = lambda k, d: g.get(f"{a}.{k}", d)  # noqa: E731
     tok = g.tensors["token_embd.weight"]
     d = int(get("embedding_length", 4096))
     heads = int(get("attention.head_count", 32))
-    return DecoderConfig(vocab=int(tok.shape[0]), d=d, layers=int(get("block_count", 32)), heads=heads,
-                         kv_heads=int(get("attention.head_count_kv", heads)), ffn=int(get("feed_forward_length", 11008)),
-                         eps=float(get("attention.layer_norm_rms_epsilon", 1e-5)),
-                         rope_base=float(get("rope.freq_base", 10000.0)), n_ctx=int(get("context_length", 2048)))
+    kl = get("attention.key_length", None)
+    cfg = DecoderConfig(vocab=int(tok.shape[0]), d=d, layers=int(get("block_count", 32)), heads=heads,
+                        kv_heads=int(get("attention.head_count_kv", heads)), ffn=int(get("feed_forward_length", 11008)),
+                        eps=float(get("attention.layer_norm_rms_epsilon", 1e-5)),
+                        rope_base=float(get("rope.freq_base", 10000.0)), n_ctx=int(get("context_length", 2048)),
+                        arch=a, qkv_bias="blk.0.attn_q.bias" in g.tensors,
+                        qk_norm="blk.0.attn_q_norm.weight" in g.tensors,
+                        key_length=int(kl) if kl is not None and int(kl) * heads != d else None)
+    rot = get("rope.dimension_count", None)
+    if rot is not None and int(rot) != cfg.head_dim:
+        raise ValueError(f"architecture {a!r} with partial rotary (rope.dimension_count {int(rot)} of head dim "
+                         f"{cfg.head_dim}) is not supported (supported: {', '.join(SUPPORTED_ARCHS)}, full rotary)")
+    kind = get("rope.scaling.type", None) or "none"
+    if kind == "linear":
+        cfg.rope_scale = float(get("rope.scaling.factor", 1.0))
+    elif kind == "yarn":
+        orig = int(get("rope.scaling.original_context_length", cfg.n_ctx))
+        cfg.n_ctx = min(cfg.n_ctx, orig)
+        print(f"[Startup]: rope scaling yarn is not applied: context window clamped to the original {cfg.n_ctx} "
+              "tokens.", flush=True)
+    elif kind != "none":
+        raise ValueError(f"architecture {a!r} with rope.scaling.type {kind!r} is not supported (none, linear, yarn)")
+    return cfg
 
 
 class Q4Weight:
@@ -199,6 +260,19 @@ class CausalLM:
             return (Q8Weight if wide else Q4Weight).quantize(self.L, t)
 
         self.head = Q(self.head, "output.weight" if "output.weight" in tensors else "token_embd.weight")
+        hd = cfg.head_dim
+        self.extras = cfg.qkv_bias or cfg.qk_norm  # the fused q/k preparation stands where RoPE stood
+        if cfg.arch in NEOX_ARCHS:
+            # NeoX rotation as adjacent pairs: permute the q / k rows of every head (and what goes with them) on
+            # the fp32 tensors, ahead of any 4- / 8-bit re-gridding (groups run along K, so rows move whole).
+            # The cache holds permuted k rows; nothing outside attention reads them.
+            tensors = dict(tensors)
+            for i in range(cfg.layers):
+                for n in ("attn_q.weight", "attn_k.weight", "attn_q.bias", "attn_k.bias", "attn_q_norm.weight",
+                          "attn_k_norm.weight"):
+                    if f"blk.{i}.{n}" in tensors:
+                        tensors[f"blk.{i}.{n}"] = neox_rows_to_pairs(tensors[f"blk.{i}.{n}"].float(), hd)
+        F32 = lambda n: tensors[n].to(device=device, dtype=torch.float32).contiguous()  # noqa: E731
         for i in range(cfg.layers):
             p = f"blk.{i}."
             qkv = torch.cat([T(p + "attn_q.weight"), T(p + "attn_k.weight"), T(p + "attn_v.weight")], 0)
@@ -212,11 +286,22 @@ class CausalLM:
                                 "n2": T(p + "ffn_norm.weight").float(),
                                 "ug": Q(ug.contiguous(), p + "ffn_gate.weight", p + "ffn_up.weight"),
                                 "down": Q(T(p + "ffn_down.weight"), p + "ffn_down.weight")})
+            # the architecture's extras, fp32: the fused bias [(H + 2 KVH) hd] and the per-head norm weights [hd]
+            lw = self.layers[-1]
+            lw["qkv_b"] = torch.cat([F32(p + f"attn_{c}.bias") for c in "qkv"]) if cfg.qkv_bias else None
+            lw["qn"] = F32(p + "attn_q_norm.weight") if cfg.qk_norm else None
+            lw["kn"] = F32(p + "attn_k_norm.weight") if cfg.qk_norm else None
             del qkv, gate, up, ug
         self._q4_scratch: Optional[torch.Tensor] = None
-        hd = cfg.head_dim
+        # RoPE tables (host only; the kernels read cos / sin): inv_freq[j] over rope_freqs.weight[j] where the
+        # file has that tensor (llama 3.1+), positions over the linear scaling factor
         inv = 1.0 / (cfg.rope_base ** (torch.arange(0, hd, 2, dtype=torch.float64) / hd))
-        ang = torch.arange(cfg.n_ctx, dtype=torch.float64)[:, None] * inv[None, :]
+        if "rope_freqs.weight" in tensors:
+            inv = inv / tensors["rope_freqs.weight"].to(torch.float64).reshape(-1)[: hd // 2]
+        rpos = torch.arange(cfg.n_ctx, dtype=torch.float64)
+        if cfg.rope_scale != 1.0:
+            rpos = rpos / cfg.rope_scale
+        ang = rpos[:, None] * inv[None, :]
         self.cos = ang.cos().float().to(device)
         self.sin = ang.sin().float().to(device)
         # KV cache: one [layers, 2, n_ctx, kv_heads, head_dim] buffer allocated on first use and
@@ -225,10 +310,13 @@ class CausalLM:
         self.pos = 0
         self.attn_kernel = True  # HIP prefill / decode attention (False: torch SDPA, for A/B only)
         if self.hip:
-            ok = all(n % 128 == 0 for n in (cfg.d + 2 * cfg.kv_heads * hd, cfg.d, 2 * cfg.ffn, vpad)) \
-                and cfg.d % 64 == 0 and cfg.ffn % 64 == 0
+            ok = all(n % 128 == 0 for n in (cfg.q_dim + 2 * cfg.kv_heads * hd, cfg.d, 2 * cfg.ffn, vpad)) \
+                and cfg.d % 64 == 0 and cfg.ffn % 64 == 0 and cfg.q_dim % 64 == 0
             if not ok:
                 raise ValueError("decoder dims must be multiples of 128 (N) / 64 (K) for the MFMA GEMM")
+            if self.extras and hd not in (64, 128):
+                raise ValueError(f"head dim {hd} with a qkv bias or q/k norms: the fused q/k preparation "
+                                 "(dec_qk_prep) takes 64 or 128")
         # HIP attention where the kernels take the head dim (prefill: 64 / 128, decode: any multiple of
         # 64 up to 256); other head dims (e.g. 80, 96) run those layers' attention on torch SDPA
         self.prefill_kernel = hd in (64, 128)
@@ -305,7 +393,22 @@ class CausalLM:
             self.L.dec_kv_rows_fanout.argtypes = [P, c_long, c_int, P, c_long, c_long, P, c_int, c_int, c_int, c_int,
                                                   c_int, c_int, P]
             self.L.dec_kv_rows_fanout.restype = c_int
+            # the fused q/k preparation (csrc/hip/decoder_arch.hip): each twin's arguments, then the fp32 bias,
+            # the q and k norm weights, the norm's eps
+            ex = [P, P, P, c_float, P]
+            self.L.dec_qk_prep.argtypes = [P, c_long, c_long, c_int, c_int, c_int, c_int, P, P] + ex
+            self.L.dec_qk_prep_kv.argtypes = self.L.dec_rope_kv.argtypes[:-1] + ex
+            self.L.dec_qk_prep_kv_b.argtypes = self.L.dec_rope_kv_b.argtypes[:-1] + ex
+            self.L.dec_qk_prep_kv_seg.argtypes = self.L.dec_rope_kv_seg.argtypes[:-1] + ex
+            for name in ("dec_qk_prep", "dec_qk_prep_kv", "dec_qk_prep_kv_b", "dec_qk_prep_kv_seg"):
+                getattr(self.L, name).restype = c_int
             self.L._dec_declared = True
+
+    def _prep_args(self, lw) -> tuple:
+        """The trailing arguments of a dec_qk_prep* call for one layer: bias, q norm, k norm (null where the
+        architecture has none), eps."""
+        P = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        return P(lw["qkv_b"]), P(lw["qn"]), P(lw["kn"]), self.cfg.eps
 
     @classmethod
     def random(cls, cfg: DecoderConfig, seed: int = 0, device: str = "cuda", quant: str = "bf16") -> "CausalLM":
@@ -398,7 +501,7 @@ class CausalLM:
     def forward(self, ids: List[int]) -> torch.Tensor:
         """Append tokens to the KV cache; returns fp32 logits of the last position."""
         cfg = self.cfg
-        hd, H, KVH = cfg.head_dim, cfg.heads, cfg.kv_heads
+        hd, H, KVH, qd = cfg.head_dim, cfg.heads, cfg.kv_heads, cfg.q_dim
         n = len(ids)
         if self.pos + n > cfg.n_ctx:
             raise ValueError("context window exceeded")
@@ -406,15 +509,25 @@ class CausalLM:
         x = self.emb[torch.tensor(ids, device=self.device)]
         for li, lw in enumerate(self.layers):
             h = self._rms(x, lw["n1"])
-            qkv = self._mm(0, h, lw["qkv"], cfg.d + 2 * KVH * hd)
-            if self.hip:  # RoPE in place over the q|k columns (dec_rope)
+            qkv = self._mm(0, h, lw["qkv"], qd + 2 * KVH * hd)
+            if self.hip and self.extras:
+                # bias, per-head RMSNorm and RoPE in place, one launch where dec_rope stands (dec_qk_prep)
                 from .nomic import _chk, _stream
-                _chk(self.L.dec_rope(qkv.data_ptr(), qkv.stride(0), n, cfg.d + KVH * hd, hd, self.pos,
+                _chk(self.L.dec_qk_prep(qkv.data_ptr(), qkv.stride(0), n, H, KVH, hd, self.pos, self.cos.data_ptr(),
+                                        self.sin.data_ptr(), *self._prep_args(lw), _stream()), "qk_prep")
+            elif self.hip:  # RoPE in place over the q|k columns (dec_rope)
+                from .nomic import _chk, _stream
+                _chk(self.L.dec_rope(qkv.data_ptr(), qkv.stride(0), n, qd + KVH * hd, hd, self.pos,
                                      self.cos.data_ptr(), self.sin.data_ptr(), _stream()), "rope")
-            q = qkv[:, : cfg.d].reshape(n, H, hd)
-            k = qkv[:, cfg.d: cfg.d + KVH * hd].reshape(n, KVH, hd)
-            v = qkv[:, cfg.d + KVH * hd:].reshape(n, KVH, hd)
+            elif lw["qkv_b"] is not None:
+                qkv = qkv + lw["qkv_b"]
+            q = qkv[:, :qd].reshape(n, H, hd)
+            k = qkv[:, qd: qd + KVH * hd].reshape(n, KVH, hd)
+            v = qkv[:, qd + KVH * hd:].reshape(n, KVH, hd)
             if not self.hip:
+                if lw["qn"] is not None:  # per-head RMSNorm of q and k, ahead of the rotation
+                    nrm = lambda t, w: t * torch.rsqrt(t.pow(2).mean(-1, keepdim=True) + cfg.eps) * w  # noqa: E731
+                    q, k = nrm(q, lw["qn"]), nrm(k, lw["kn"])
                 q, k = self._rope(q, pos), self._rope(k, pos)
             if self.kv is None:
                 self.kv = torch.empty((cfg.layers, 2, cfg.n_ctx, KVH, hd), dtype=qkv.dtype, device=self.device)
@@ -425,15 +538,15 @@ class CausalLM:
                 # prompt prefill, fresh or continuing a live cache: causal MFMA attention of the n new
                 # queries over cache rows 0 .. pos+n-1 (dec_attn_prefill_kv, hd 64 / 128)
                 from .nomic import _chk, _stream
-                a = torch.empty((n, cfg.d), dtype=qkv.dtype, device=self.device)
+                a = torch.empty((n, qd), dtype=qkv.dtype, device=self.device)
                 _chk(self.L.dec_attn_prefill_kv(qkv.data_ptr(), qkv.stride(0), self.kv[li, 0].data_ptr(),
                                                 self.kv[li, 1].data_ptr(), KVH * hd, n, self.pos, H, KVH, hd,
-                                                hd ** -0.5, a.data_ptr(), cfg.d, _stream()), "attn_prefill")
+                                                hd ** -0.5, a.data_ptr(), qd, _stream()), "attn_prefill")
             elif self.hip and self.attn_kernel and self.decode_kernel and n == 1:
                 # per-token decode: dec_attn_decode (one workgroup per q head, split-L online softmax)
                 from .nomic import _chk, _stream
-                a = torch.empty((1, cfg.d), dtype=qkv.dtype, device=self.device)
-                qrow = qkv[0, : cfg.d].contiguous()
+                a = torch.empty((1, qd), dtype=qkv.dtype, device=self.device)
+                qrow = qkv[0, :qd].contiguous()
                 _chk(self.L.dec_attn_decode(qrow.data_ptr(), self.kv[li, 0].data_ptr(), self.kv[li, 1].data_ptr(),
                                             KVH * hd, L_, H, KVH, hd, hd ** -0.5, a.data_ptr(), _stream()),
                      "attn_decode")
@@ -450,7 +563,7 @@ class CausalLM:
                 a = torch.nn.functional.scaled_dot_product_attention(qh.unsqueeze(0), kh.unsqueeze(0),
                                                                      vh.unsqueeze(0), attn_mask=mask,
                                                                      is_causal=fresh, enable_gqa=KVH != H)[0]
-                a = a.transpose(0, 1).reshape(n, cfg.d).contiguous()
+                a = a.transpose(0, 1).reshape(n, qd).contiguous()
             x = self._mm(1, a, lw["o"], cfg.d, res=x)
             h = self._rms(x, lw["n2"])
             f = self._mm(2, h, lw["ug"], cfg.ffn)
@@ -508,8 +621,8 @@ class DecodeEngine:
         self.st = torch.zeros(4, dtype=torch.int32, device=dev)      # pos, token, step
         self.xa = torch.empty(cfg.d, **e)
         self.xb = torch.empty(cfg.d, **e)
-        self.qkv = torch.empty(cfg.d + 2 * kvd, **e)
-        self.attn = torch.empty(cfg.d, **e)
+        self.qkv = torch.empty(cfg.q_dim + 2 * kvd, **e)
+        self.attn = torch.empty(cfg.q_dim, **e)
         self.ffn = torch.empty(cfg.ffn, **e)
         self.logits = torch.empty(m.head.shape[0], dtype=torch.float32, device=dev)
         self.attn_ws = torch.empty(cfg.heads * 32 * (cfg.head_dim + 2), dtype=torch.float32, device=dev)  # split-L
@@ -541,14 +654,19 @@ class DecodeEngine:
         for li, lw in enumerate(m.layers):
             gemv(0, self.xa, lw["n1"], lw["qkv"], lw["qkv"].shape[0], cfg.d, None, self.qkv, "gemv qkv")
             kc, vc = m.kv[li, 0], m.kv[li, 1]
-            _chk(L.dec_rope_kv(self.qkv.data_ptr(), H, KVH, hd, m.cos.data_ptr(), m.sin.data_ptr(), self.st.data_ptr(),
-                               kc.data_ptr(), vc.data_ptr(), KVH * hd, s), "rope_kv")
+            if m.extras:  # bias, per-head RMSNorm, RoPE and the cache append in the one launch (dec_qk_prep_kv)
+                _chk(L.dec_qk_prep_kv(self.qkv.data_ptr(), H, KVH, hd, m.cos.data_ptr(), m.sin.data_ptr(),
+                                      self.st.data_ptr(), kc.data_ptr(), vc.data_ptr(), KVH * hd, *m._prep_args(lw), s),
+                     "qk_prep_kv")
+            else:
+                _chk(L.dec_rope_kv(self.qkv.data_ptr(), H, KVH, hd, m.cos.data_ptr(), m.sin.data_ptr(),
+                                   self.st.data_ptr(), kc.data_ptr(), vc.data_ptr(), KVH * hd, s), "rope_kv")
             # L = the span the step is captured for (<= 512: one workgroup per head group; else the
             # capacity, sizing the split-L grid); the length itself is read on the device
             _chk(L.dec_attn_decode_ws(self.qkv.data_ptr(), kc.data_ptr(), vc.data_ptr(), KVH * hd, span or cfg.n_ctx, H, KVH,
                                       hd, hd ** -0.5, self.attn.data_ptr(), self.st.data_ptr(),
                                       self.attn_ws.data_ptr(), s), "attn_decode")
-            gemv(1, self.attn, None, lw["o"], cfg.d, cfg.d, self.xa, self.xb, "gemv o")
+            gemv(1, self.attn, None, lw["o"], cfg.d, cfg.q_dim, self.xa, self.xb, "gemv o")
             gemv(2, self.xb, lw["n2"], lw["ug"], lw["ug"].shape[0], cfg.d, None, self.ffn, "gemv up|gate")
             gemv(1, self.ffn, None, lw["down"], cfg.d, cfg.ffn, self.xb, self.xa, "gemv down")
         gemv(4, self.xa, m.norm_out, m.head, m.head.shape[0], cfg.d, None, self.logits, "gemv head")
@@ -650,7 +768,7 @@ class BatchDecodeEngine:
                               device=dev)
         z = lambda n, dt=torch.bfloat16: torch.zeros((S, n), dtype=dt, device=dev)  # noqa: E731
         self.xa, self.xb, self.h = z(cfg.d), z(cfg.d), z(cfg.d)
-        self.qkv, self.attn, self.ffn = z(cfg.d + 2 * kvd), z(cfg.d), z(cfg.ffn)
+        self.qkv, self.attn, self.ffn = z(cfg.q_dim + 2 * kvd), z(cfg.q_dim), z(cfg.ffn)
         self.logits = z(m.head.shape[0], torch.float32)
         self.st = torch.zeros((S, self.ST_WORDS), dtype=torch.int32, device=dev)
         self.attn_ws = torch.empty(m.L.dec_attn_b_ws_floats(S, cfg.heads, cfg.head_dim), dtype=torch.float32,
@@ -806,7 +924,7 @@ class BatchDecodeEngine:
         kvd = cfg.kv_heads * cfg.head_dim
         z = lambda r, n, dt=torch.bfloat16: torch.zeros((r, n), dtype=dt, device=dev)  # noqa: E731
         w = {"rows": rows, "x": z(rows, cfg.d), "xb": z(rows, cfg.d), "h": z(rows, cfg.d),
-             "qkv": z(rows, cfg.d + 2 * kvd), "attn": z(rows, cfg.d), "ffn": z(rows, cfg.ffn),
+             "qkv": z(rows, cfg.q_dim + 2 * kvd), "attn": z(rows, cfg.q_dim), "ffn": z(rows, cfg.ffn),
              "last": z(self.PF_ROWS, cfg.d), "hl": z(self.PF_ROWS, cfg.d),
              "lg": z(self.PF_ROWS, self.m.head.shape[0], torch.float32),
              "ids": torch.zeros(rows, dtype=torch.int64, device=dev),
@@ -899,9 +1017,14 @@ class BatchDecodeEngine:
                 rms(x, lw["n1"], h, T)
                 self._pf_mm(0, h, T, lw["qkv"], None, qkv, "gemm qkv")
                 kc, vc = self.kv[0, li, 0], self.kv[0, li, 1]
-                _chk(L.dec_rope_kv_seg(qkv.data_ptr(), qkv.stride(0), T, tp, ns, H, KVH, hd, m.cos.data_ptr(),
-                                       m.sin.data_ptr(), kc.data_ptr(), vc.data_ptr(), KVH * hd, self.kv.stride(0),
-                                       S, cfg.n_ctx, s), "rope_kv_seg")
+                if m.extras:
+                    _chk(L.dec_qk_prep_kv_seg(qkv.data_ptr(), qkv.stride(0), T, tp, ns, H, KVH, hd, m.cos.data_ptr(),
+                                              m.sin.data_ptr(), kc.data_ptr(), vc.data_ptr(), KVH * hd,
+                                              self.kv.stride(0), S, cfg.n_ctx, *m._prep_args(lw), s), "qk_prep_kv_seg")
+                else:
+                    _chk(L.dec_rope_kv_seg(qkv.data_ptr(), qkv.stride(0), T, tp, ns, H, KVH, hd, m.cos.data_ptr(),
+                                           m.sin.data_ptr(), kc.data_ptr(), vc.data_ptr(), KVH * hd,
+                                           self.kv.stride(0), S, cfg.n_ctx, s), "rope_kv_seg")
                 _chk(L.dec_attn_prefill_kv_seg(qkv.data_ptr(), qkv.stride(0), T, tp, ns, kc.data_ptr(), vc.data_ptr(),
                                                KVH * hd, self.kv.stride(0), S, cfg.n_ctx, H, KVH, hd, hd ** -0.5,
                                                attn.data_ptr(), attn.stride(0), s), "attn_prefill_kv_seg")
@@ -976,13 +1099,18 @@ class BatchDecodeEngine:
             rms(self.xa, lw["n1"], self.h)
             self._mm(0, self.h, lw["qkv"], lw["qkv"].shape[0], cfg.d, None, self.qkv, "gemm qkv")
             kc, vc = self.kv[0, li, 0], self.kv[0, li, 1]
-            _chk(L.dec_rope_kv_b(self.qkv.data_ptr(), self.qkv.stride(0), S, H, KVH, hd, m.cos.data_ptr(),
-                                 m.sin.data_ptr(), st, kc.data_ptr(), vc.data_ptr(), KVH * hd, self.kv.stride(0), s),
-                 "rope_kv_b")
+            if m.extras:
+                _chk(L.dec_qk_prep_kv_b(self.qkv.data_ptr(), self.qkv.stride(0), S, H, KVH, hd, m.cos.data_ptr(),
+                                        m.sin.data_ptr(), st, kc.data_ptr(), vc.data_ptr(), KVH * hd,
+                                        self.kv.stride(0), *m._prep_args(lw), s), "qk_prep_kv_b")
+            else:
+                _chk(L.dec_rope_kv_b(self.qkv.data_ptr(), self.qkv.stride(0), S, H, KVH, hd, m.cos.data_ptr(),
+                                     m.sin.data_ptr(), st, kc.data_ptr(), vc.data_ptr(), KVH * hd, self.kv.stride(0),
+                                     s), "rope_kv_b")
             _chk(L.dec_attn_decode_b(self.qkv.data_ptr(), self.qkv.stride(0), kc.data_ptr(), vc.data_ptr(), KVH * hd,
                                      self.kv.stride(0), span, S, H, KVH, hd, hd ** -0.5, self.attn.data_ptr(),
                                      self.attn.stride(0), st, self.attn_ws.data_ptr(), s), "attn_decode_b")
-            self._mm(1, self.attn, lw["o"], cfg.d, cfg.d, self.xa, self.xb, "gemm o")
+            self._mm(1, self.attn, lw["o"], cfg.d, cfg.q_dim, self.xa, self.xb, "gemm o")
             rms(self.xb, lw["n2"], self.h)
             self._mm(2, self.h, lw["ug"], lw["ug"].shape[0], cfg.d, None, self.ffn, "gemm up|gate")
             self._mm(1, self.ffn, lw["down"], cfg.d, cfg.ffn, self.xb, self.xa, "gemm down")

@@ -1,20 +1,54 @@
-"""Per-token decode latency of the splainference decoder: dec_attn_decode vs torch SDPA (A/B).
+"""Per-token decode latency of the splainference decoder.
 
-Random-init 7B-shaped layers are too big for a quick A/B, so this uses the default DecoderConfig
-with --layers layers, prefills --prefill tokens, then times --steps single-token decode steps."""
+Default: dec_attn_decode vs torch SDPA (A/B) on the eager forward.  Random-init 7B-shaped layers are too big
+for a quick A/B, so this uses the default DecoderConfig with --layers layers, prefills --prefill tokens, then
+times --steps single-token decode steps.
+
+--engine: ms/token of DecodeEngine steps (the captured decode step; --no-graph: eager launches) for one
+architecture, --arch llama | qwen2 | qwen3: qwen2 adds the q/k/v biases, qwen3 the per-head q/k norms, so the
+step runs dec_qk_prep_kv where the llama step runs dec_rope_kv.  --d / --heads / --kv-heads / --head-dim /
+--ffn set the layer shape, --quant the weights; --repeats timed blocks of --steps tokens give the spread."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from libsplinter_amd.models.decoder import CausalLM, DecoderConfig
+from libsplinter_amd.models.decoder import CausalLM, DecodeEngine, DecoderConfig
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--layers", type=int, default=4)
 ap.add_argument("--prefill", type=int, default=1024)
 ap.add_argument("--steps", type=int, default=128)
 ap.add_argument("--kv-heads", type=int, default=8)
+ap.add_argument("--arch", default="llama", choices=["llama", "qwen2", "qwen3"])
+ap.add_argument("--engine", action="store_true")
+ap.add_argument("--no-graph", action="store_true")
+ap.add_argument("--quant", default="bf16", choices=["bf16", "q4"])
+ap.add_argument("--d", type=int, default=512)
+ap.add_argument("--heads", type=int, default=8)
+ap.add_argument("--head-dim", type=int, default=0, help="0: d / heads")
+ap.add_argument("--ffn", type=int, default=1536)
+ap.add_argument("--repeats", type=int, default=1)
 a = ap.parse_args()
-cfg = DecoderConfig(layers=a.layers, kv_heads=a.kv_heads, n_ctx=a.prefill + a.steps + 8)
-m = CausalLM.random(cfg, seed=0, device="cuda")
+cfg = DecoderConfig(layers=a.layers, kv_heads=a.kv_heads, d=a.d, heads=a.heads, ffn=a.ffn, arch=a.arch,
+                    qkv_bias=a.arch == "qwen2", qk_norm=a.arch == "qwen3",
+                    key_length=a.head_dim if a.head_dim and a.head_dim * a.heads != a.d else None,
+                    n_ctx=a.prefill + (a.steps * max(1, a.repeats) + 16 if a.engine else a.steps + 8))
+m = CausalLM.random(cfg, seed=0, device="cuda", quant=a.quant)
+shape = {"arch": a.arch, "quant": a.quant, "layers": a.layers, "ctx": a.prefill, "d": cfg.d, "heads": cfg.heads,
+         "kv_heads": a.kv_heads, "head_dim": cfg.head_dim, "ffn": cfg.ffn}
+if a.engine:
+    eng = DecodeEngine(m, use_graph=not a.no_graph)
+    eng.first_token([1] * a.prefill)
+    for _ in range(8):
+        eng.next_token()
+    ms = []
+    for _ in range(a.repeats):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(a.steps):
+            eng.next_token()
+        ms.append(round((time.perf_counter() - t0) / a.steps * 1e3, 5))
+    print(json.dumps({"engine_ms_per_token": ms, "graph": not a.no_graph, "steps": a.steps, **shape}))
+    sys.exit(0)
 res = {}
 for mode in (False, True, False, True):
     m.attn_kernel = mode
