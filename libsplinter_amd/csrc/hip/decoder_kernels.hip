@@ -983,7 +983,7 @@ int dec_attn_prefill_kv_seg(const void* q, long ldq, long T, const int32_t* segs
 int dec_attn_decode_ws(const void* q, const void* k, const void* v, long ldkv, int L, int H, int KVH, int hd,
                        float scale, void* out, const int32_t* st, float* ws, hipStream_t s) {
   if (L <= 0 || H <= 0 || KVH <= 0 || H % KVH || hd <= 0 || hd % 64 || hd > 256 || ldkv % 8 ||
-      ldkv < (long)KVH * hd || ((uintptr_t)k | (uintptr_t)v) % 16)
+      ldkv < (long)KVH * hd || ((uintptr_t)k | (uintptr_t)v | (uintptr_t)q) % 16)  // q: 16-B loads in k_attn_decode_g
     return (int)hipErrorInvalidValue;
   const int grp = H / KVH;
   const int S = decode_splits(L);
