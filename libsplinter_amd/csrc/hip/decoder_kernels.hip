@@ -27,6 +27,7 @@
 #include <type_traits>
 
 #include "decoder_common.hpp"
+#include "decoder_gemv.hpp"
 
 namespace {
 
@@ -158,147 +159,13 @@ __global__ void k_attn_combine(const float* __restrict__ ws, int S, int hd, uint
 // ------------------------------------------------------------------ decode step --
 // The device state record {pos, token, step} and the wave reductions: decoder_common.hpp.
 
-// y[n] = x . W[n, :] for one token.  x (bf16 [K], optionally RMS-normalised in LDS first: the
-// dec_rmsnorm + GEMV pair of a layer in one launch) is staged in LDS; each wave owns 4 weight rows
-// and streams them with 16-B loads, 4 independent accumulators in flight.  MODE 0: bf16 out,
-// 1: + residual (bf16, may alias out: each element is read and written by the same lane),
-// 2: SwiGLU over pack_upgate rows (out[o] = up * silu(gate), o -> rows 32(o/16) + o%16 and +16),
-// 4: fp32 out (logits).
-constexpr int kGemvRows = 4;
-constexpr int kGemvMaxK = 16384;
-
-// The row map and the store epilogue shared by k_gemv and k_gemv_q4.  A wave's R weight rows serve
-// outputs o0, o0 + 1, ..: row r is output o0 + r, or with MODE 2 the up (r even) / gate (r odd) row
-// of output o0 + r / 2 in pack_upgate's 32-row blocks.
-template <int MODE, int R>
-__device__ __forceinline__ void gemv_rows(int o0, int nout, long (&rows)[R]) {
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    int o = o0 + (MODE == 2 ? r / 2 : r);
-    if (o >= nout) o = nout - 1;  // tail: recompute the last output, never stored twice
-    rows[r] = MODE == 2 ? (long)(32 * (o / 16) + (o % 16) + (r & 1) * 16) : (long)o;
-  }
-}
-// acc: the rows' wave-reduced dot products; lane i stores output o0 + i
-template <int MODE, int R>
-__device__ __forceinline__ void gemv_store(const float (&acc)[R], int o0, int nout, int lane, const uint16_t* res,
-                                           void* out) {
-  constexpr int outs = MODE == 2 ? R / 2 : R;
-  if (lane < outs) {
-    const int o = o0 + lane;
-    if (o < nout) {
-      float a0 = acc[0], a1 = acc[1];
-#pragma unroll
-      for (int r = 0; r < R; ++r)
-        if ((MODE == 2 ? r / 2 : r) == lane) {
-          if (MODE == 2) { if (r & 1) a1 = acc[r]; else a0 = acc[r]; }
-          else a0 = acc[r];
-        }
-      if constexpr (MODE == 4) {
-        ((float*)out)[o] = a0;
-      } else {
-        float y = a0;
-        if constexpr (MODE == 1) y += bf2f(res[o]);
-        if constexpr (MODE == 2) y = a0 * a1 / (1.f + __expf(-a1));
-        ((uint16_t*)out)[o] = __builtin_bit_cast(uint16_t, (__bf16)y);
-      }
-    }
-  }
-}
-
+// The one-token GEMV: geometry, row map, store epilogue and the Q4G32 / Q8G32 layout are in decoder_gemv.hpp,
+// the loop text in decoder_body_gemv.hpp / decoder_body_gemv_q4.hpp (shared with decoder_moe.hip).
 template <int MODE, bool RMS>
 __global__ __launch_bounds__(256) void k_gemv(const uint16_t* __restrict__ x, const float* __restrict__ rw, float eps,
                                               const uint16_t* __restrict__ W, int K, int nout,
                                               const uint16_t* res, void* out) {
-  __shared__ __attribute__((aligned(16))) uint16_t xs[kGemvMaxK];
-  __shared__ float red[4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int nch = K >> 3;
-  // this wave's outputs and their weight rows; the first chunk of every row is requested BEFORE x
-  // is staged, so its HBM latency overlaps the staging and the barriers (as k_gemv_q4)
-  constexpr int outs = MODE == 2 ? kGemvRows / 2 : kGemvRows;
-  const int o0 = (blockIdx.x * 4 + wave) * outs;
-  const bool active = o0 < nout;
-  long rows[kGemvRows];
-  gemv_rows<MODE>(o0, nout, rows);
-  uint4 wv[kGemvRows];
-  if (active && lane < nch) {
-#pragma unroll
-    for (int r = 0; r < kGemvRows; ++r) wv[r] = *(const uint4*)(W + rows[r] * K + lane * 8);
-  }
-  float ss = 0.f;
-  for (int c = tid; c < nch; c += 256) {
-    const uint4 v = *(const uint4*)(x + c * 8);
-    *(uint4*)(xs + c * 8) = v;
-    if constexpr (RMS) {
-      float f[8];
-      unpack8(v, f);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) ss += f[e] * f[e];
-    }
-  }
-  if constexpr (RMS) {
-    ss = wave_sum(ss);
-    if (lane == 0) red[wave] = ss;
-    __syncthreads();
-    const float rs = rsqrtf((red[0] + red[1] + red[2] + red[3]) / (float)K + eps);
-    for (int c = tid; c < nch; c += 256) {  // each thread rewrites the chunks it staged
-      float f[8];
-      unpack8(*(const uint4*)(xs + c * 8), f);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) f[e] = f[e] * rs * rw[c * 8 + e];
-      *(uint4*)(xs + c * 8) = pack8(f);
-    }
-  }
-  __syncthreads();
-  if (!active) return;
-  float acc[kGemvRows] = {};
-  for (int c = lane; c < nch; c += 64) {
-    uint4 cw[kGemvRows];
-#pragma unroll
-    for (int r = 0; r < kGemvRows; ++r) cw[r] = wv[r];
-    if (c + 64 < nch) {  // one chunk of look-ahead per row
-#pragma unroll
-      for (int r = 0; r < kGemvRows; ++r) wv[r] = *(const uint4*)(W + rows[r] * K + (c + 64) * 8);
-    }
-    float xf[8];
-    unpack8(*(const uint4*)(xs + c * 8), xf);
-#pragma unroll
-    for (int r = 0; r < kGemvRows; ++r) {
-      float wf[8];
-      unpack8(cw[r], wf);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) acc[r] += wf[e] * xf[e];
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < kGemvRows; ++r) acc[r] = wave_sum(acc[r]);
-  gemv_store<MODE>(acc, o0, nout, lane, res, out);
-}
-
-// ---------------------------------------------------------------------------
-// 4-bit weights (Q4G32): W [N, K] resident in HBM at 0.625 B per weight instead of 2.
-//   q  : uint8 [N, K/2]  -- k = 2j in the low nibble of byte j, k = 2j + 1 in the high nibble
-//   sm : uint32 [N, K/32] -- per 32-k group, bf16 pair (d low, m high): w = d * q + m
-// The decode step is weight-bandwidth bound (every weight read once per token), so the GEMV reads
-// 3.2x fewer bytes than the bf16 one.  GGUF Q4_0 / Q4_1 / Q4_K blocks are all affine 4-bit grids
-// over 32-weight (sub)blocks, which is the layout this format keeps (reference: llama.cpp reads
-// its Q4 weights directly in llama_decode, splainference.cpp:272-330).
-// ---------------------------------------------------------------------------
-constexpr int kQ4Group = 32;
-
-// nibble pairs -> floats: for one dword of 8 nibbles (k = 0..7), lo bytes hold k = 0,2,4,6 and hi
-// bytes k = 1,3,5,7; each byte converts with a single v_cvt_f32_ubyteN
-__device__ __forceinline__ float q4dot8(uint32_t w, const float* x) {
-  const uint32_t lo = w & 0x0F0F0F0Fu, hi = (w >> 4) & 0x0F0F0F0Fu;
-  float s = (float)(lo & 0xff) * x[0];
-  s = fmaf((float)(hi & 0xff), x[1], s);
-  s = fmaf((float)((lo >> 8) & 0xff), x[2], s);
-  s = fmaf((float)((hi >> 8) & 0xff), x[3], s);
-  s = fmaf((float)((lo >> 16) & 0xff), x[4], s);
-  s = fmaf((float)((hi >> 16) & 0xff), x[5], s);
-  s = fmaf((float)(lo >> 24), x[6], s);
-  return fmaf((float)(hi >> 24), x[7], s);
+#include "decoder_body_gemv.hpp"
 }
 
 // y[n] = x . W[n, :] with W in Q4G32.  Structure of k_gemv: x (optionally RMS-normalised) staged
@@ -307,17 +174,6 @@ __device__ __forceinline__ float q4dot8(uint32_t w, const float* x) {
 // and iteration (one 16-B load of nibbles + one scale word per row).
 // Measured and removed: 8 rows per wave (SPL_Q4_ROWS=8: 222 VGPRs, 2 waves per SIMD), 0.788 against
 // 0.713 ms/token (profiles/r2_decode_q4.md, r2_q4_rows_ab.jsonl).
-constexpr int kGemvQ4MaxK = 16384;
-constexpr int kQ4Rec = kQ4Group + 4;  // LDS floats per group record
-
-// 8-bit bytes -> floats, one v_cvt_f32_ubyteN each (Q8G32: k = 4j .. 4j+3 in dword j)
-__device__ __forceinline__ float q8dot4(uint32_t w, const float* x) {
-  float s = (float)(w & 0xff) * x[0];
-  s = fmaf((float)((w >> 8) & 0xff), x[1], s);
-  s = fmaf((float)((w >> 16) & 0xff), x[2], s);
-  return fmaf((float)(w >> 24), x[3], s);
-}
-
 // BITS 4: Q4G32 nibbles (16 B per group); BITS 8: Q8G32 bytes (32 B per group, the same (d, m)
 // words: w = d * u + m with u in 0..255) -- the >4-bit GGUF tensors (Q6_K / Q5_x / Q8_0 / F16) of a
 // mostly-4-bit file keep >= 6 bits instead of being re-gridded to 4
@@ -326,122 +182,7 @@ __global__ __launch_bounds__(256) void k_gemv_q4(const uint16_t* __restrict__ x,
                                                  float eps, const uint8_t* __restrict__ Wq,
                                                  const uint32_t* __restrict__ Wsm, int K, int nout,
                                                  const uint16_t* res, void* out) {
-  // dynamic LDS, fp32, one 36-float record per 32-k group: x[32], the group sum, 3 pad.  The
-  // 144-B record stride keeps the main loop's per-lane ds_read_b128 of consecutive groups
-  // conflict-free (16-lane phases start on 16 distinct 4-bank quads).
-  extern __shared__ __attribute__((aligned(16))) float xs[];
-  __shared__ float red[4];
-  constexpr int R = kGemvRows;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int nch = K >> 3, ng = K / kQ4Group;
-  // this wave's weight rows, and its first group's weights requested BEFORE x is staged: the HBM
-  // latency of the first loads overlaps the staging and its barriers
-  constexpr int outs = MODE == 2 ? R / 2 : R;
-  const int o0 = (blockIdx.x * 4 + wave) * outs;
-  const bool active = o0 < nout;
-  long rows[R];
-  gemv_rows<MODE>(o0, nout, rows);
-  constexpr int GV = BITS / 4;  // 16-B loads per group and row
-  const long qrow = (long)K * BITS / 8;
-  uint4 wq[R][GV];
-  uint32_t sm[R];
-  if (active && lane < ng) {
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-#pragma unroll
-      for (int v = 0; v < GV; ++v) wq[r][v] = *(const uint4*)(Wq + rows[r] * qrow + lane * 16 * GV + v * 16);
-      sm[r] = Wsm[rows[r] * ng + lane];
-    }
-  }
-  float ss = 0.f;
-  for (int c = tid; c < nch; c += 256) {
-    float f[8];
-    unpack8(*(const uint4*)(x + c * 8), f);
-    float* px = xs + (c >> 2) * kQ4Rec + (c & 3) * 8;
-    *(float4*)px = make_float4(f[0], f[1], f[2], f[3]);
-    *(float4*)(px + 4) = make_float4(f[4], f[5], f[6], f[7]);
-    if constexpr (RMS) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) ss += f[e] * f[e];
-    }
-  }
-  float rs = 1.f;
-  if constexpr (RMS) {
-    ss = wave_sum(ss);
-    if (lane == 0) red[wave] = ss;
-    __syncthreads();
-    rs = rsqrtf((red[0] + red[1] + red[2] + red[3]) / (float)K + eps);
-  }
-  // each thread revisits the chunks it staged: RMS scaling (x * rs * w rounded to bf16, as the bf16
-  // path feeds its GEMV) and the 32-group sums over the 4 consecutive lanes holding a group's chunks
-  // (nch % 4 == 0 and the stride 256 keep a group's 4 lanes active together)
-  for (int c = tid; c < nch; c += 256) {
-    float* px = xs + (c >> 2) * kQ4Rec + (c & 3) * 8;
-    float4 a = *(const float4*)px, b = *(const float4*)(px + 4);
-    if constexpr (RMS) {
-      const float4 wa = *(const float4*)(rw + c * 8), wb = *(const float4*)(rw + c * 8 + 4);
-      a = make_float4((float)(__bf16)(a.x * rs * wa.x), (float)(__bf16)(a.y * rs * wa.y),
-                      (float)(__bf16)(a.z * rs * wa.z), (float)(__bf16)(a.w * rs * wa.w));
-      b = make_float4((float)(__bf16)(b.x * rs * wb.x), (float)(__bf16)(b.y * rs * wb.y),
-                      (float)(__bf16)(b.z * rs * wb.z), (float)(__bf16)(b.w * rs * wb.w));
-      *(float4*)px = a;
-      *(float4*)(px + 4) = b;
-    }
-    float s = ((a.x + a.y) + (a.z + a.w)) + ((b.x + b.y) + (b.z + b.w));
-    s += __shfl_xor(s, 1, 64);
-    s += __shfl_xor(s, 2, 64);
-    if ((c & 3) == 0) xs[(c >> 2) * kQ4Rec + kQ4Group] = s;
-  }
-  __syncthreads();
-  if (!active) return;
-  float acc[R] = {};
-  for (int g = lane; g < ng; g += 64) {
-    // the group's weights are in registers; request the next group's before the math (one group
-    // of look-ahead per lane: 2 x 4 x 20 B in flight)
-    uint4 cq[R][GV];
-    uint32_t csm[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-#pragma unroll
-      for (int v = 0; v < GV; ++v) cq[r][v] = wq[r][v];
-      csm[r] = sm[r];
-    }
-    if (g + 64 < ng) {
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-#pragma unroll
-        for (int v = 0; v < GV; ++v) wq[r][v] = *(const uint4*)(Wq + rows[r] * qrow + (g + 64) * 16 * GV + v * 16);
-        sm[r] = Wsm[rows[r] * ng + g + 64];
-      }
-    }
-    float xg[kQ4Group];
-#pragma unroll
-    for (int e = 0; e < kQ4Group; e += 4) *(float4*)(xg + e) = *(const float4*)(xs + g * kQ4Rec + e);
-    const float gs = xs[g * kQ4Rec + kQ4Group];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      float dot;
-      if constexpr (BITS == 4) {
-        dot = q4dot8(cq[r][0].x, xg);
-        dot += q4dot8(cq[r][0].y, xg + 8);
-        dot += q4dot8(cq[r][0].z, xg + 16);
-        dot += q4dot8(cq[r][0].w, xg + 24);
-      } else {
-        dot = q8dot4(cq[r][0].x, xg);
-        dot += q8dot4(cq[r][0].y, xg + 4);
-        dot += q8dot4(cq[r][0].z, xg + 8);
-        dot += q8dot4(cq[r][0].w, xg + 12);
-        dot += q8dot4(cq[r][GV - 1].x, xg + 16);
-        dot += q8dot4(cq[r][GV - 1].y, xg + 20);
-        dot += q8dot4(cq[r][GV - 1].z, xg + 24);
-        dot += q8dot4(cq[r][GV - 1].w, xg + 28);
-      }
-      acc[r] = fmaf(bf2f(csm[r] & 0xffff), dot, fmaf(bf2f(csm[r] >> 16), gs, acc[r]));
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < R; ++r) acc[r] = wave_sum(acc[r]);
-  gemv_store<MODE>(acc, o0, nout, lane, res, out);
+#include "decoder_body_gemv_q4.hpp"
 }
 
 // bf16 W [N, K] -> Q4G32 (one thread per 32-weight group): affine min/max grid, d and m rounded

@@ -175,6 +175,10 @@ class Splainference:
         if batch > 1 and not gpu:
             print(f"[Warn]: --batch {batch} needs the GPU decode kernels; serving one request at a time.", flush=True)
             batch = 1
+        if gpu and batch > 1 and getattr(getattr(model, "cfg", None), "experts", 0):
+            print(f"[Warn]: --batch {batch} has no mixture-of-experts decode step; serving one request at a time.",
+                  flush=True)
+            batch = 1
         if gpu and batch > 1:
             from ..models.decoder import BatchDecodeEngine
             self.batch_engine = BatchDecodeEngine(model, batch, sampler.top_p, sampler.temp, sampler.seed,

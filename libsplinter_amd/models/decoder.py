@@ -10,8 +10,11 @@ the MI355X replacement, demo-grade as SURVEY §2.1 N8 scopes it:
   output) dequantised on the device, or random init (``DecoderConfig``); arch "qwen2" adds
   blk.N.attn_{q,k,v}.bias, arch "qwen3" blk.N.attn_{q,k}_norm.weight and a head dim of its own
   (attention.key_length); their NeoX rotation becomes the adjacent-pair one by a row permutation at load,
-  and bias + q/k norm + RoPE (+ cache append) are one fused launch (``csrc/hip/decoder_arch.hip``); any
-  other architecture is refused (``config_from_gguf``);
+  and bias + q/k norm + RoPE (+ cache append) are one fused launch (``csrc/hip/decoder_arch.hip``); arch
+  "qwen3moe", and "llama" with expert_count > 0 (mixtral), replace every layer's feed-forward by a mixture of
+  experts (blk.N.ffn_gate_inp, ffn_{gate,up,down}_exps stacked over the experts): the k largest router logits
+  pick each token's experts, on the device (``csrc/hip/decoder_moe.hip``); any other architecture or expert
+  layout is refused (``config_from_gguf``);
 * every projection (q|k|v fused, o + residual, gate|up + SwiGLU, down +
   residual, LM head) runs on the gfx950 MFMA GEMM (``nomic_gemm``) with its
   fused epilogues; RMSNorm and RoPE (llama "normal" adjacent-pair rotation, as
@@ -32,6 +35,8 @@ from __future__ import annotations
 
 import ctypes
 import math
+import re
+from collections.abc import Mapping
 from dataclasses import dataclass
 from typing import Dict, List, Optional
 
@@ -57,6 +62,9 @@ class DecoderConfig:
     qk_norm: bool = False     # blk.N.attn_{q,k}_norm.weight, a per-head RMSNorm ahead of the rotation (qwen3)
     key_length: Optional[int] = None  # {arch}.attention.key_length: the head dim where heads * head_dim != d
     rope_scale: float = 1.0   # rope.scaling.factor of type "linear": positions are divided by it
+    experts: int = 0          # {arch}.expert_count: 0 is a dense feed-forward, else every layer is mixture-of-experts
+    experts_used: int = 0     # {arch}.expert_used_count: experts per token (k)
+    expert_ffn: int = 0       # {arch}.expert_feed_forward_length: an expert's hidden width (F)
 
     @property
     def head_dim(self) -> int:
@@ -70,8 +78,10 @@ class DecoderConfig:
 
 # general.architecture values CausalLM computes (mistral files say "llama"); qwen2 / qwen3 rotate the halves
 # of a head against each other (NeoX), which the loader turns into adjacent pairs by permuting rows
-SUPPORTED_ARCHS = ("llama", "qwen2", "qwen3")
-NEOX_ARCHS = ("qwen2", "qwen3")
+SUPPORTED_ARCHS = ("llama", "qwen2", "qwen3", "qwen3moe")
+NEOX_ARCHS = ("qwen2", "qwen3", "qwen3moe")
+# mixture-of-experts limits of the router kernel (csrc/hip/decoder_moe.hip) and the one-token GEMV's K
+MOE_MAX_EXPERTS, MOE_MAX_USED, GEMV_MAX_K = 256, 8, 16384
 
 
 def neox_rows_to_pairs(t: torch.Tensor, hd: int) -> torch.Tensor:
@@ -118,6 +128,8 @@ def random_decoder_weights(cfg: DecoderConfig, seed: int = 0, std: float = 0.02)
         w[p + "attn_v.weight"] = f(kvd, cfg.d)
         w[p + "attn_output.weight"] = f(cfg.d, cfg.q_dim)
         w[p + "ffn_norm.weight"] = np.ones(cfg.d, np.float32)
+        if cfg.experts:
+            continue
         w[p + "ffn_gate.weight"] = f(cfg.ffn, cfg.d)
         w[p + "ffn_up.weight"] = f(cfg.ffn, cfg.d)
         w[p + "ffn_down.weight"] = f(cfg.d, cfg.ffn)
@@ -130,15 +142,55 @@ def random_decoder_weights(cfg: DecoderConfig, seed: int = 0, std: float = 0.02)
         if cfg.qk_norm:
             for n in ("q", "k"):
                 w[p + f"attn_{n}_norm.weight"] = (1.0 + 0.1 * rng.standard_normal(cfg.head_dim)).astype(np.float32)
+    # the experts come last of all: router [E, d], gate / up [E, F, d], down [E, d, F]
+    for i in range(cfg.layers if cfg.experts else 0):
+        p = f"blk.{i}."
+        w[p + "ffn_gate_inp.weight"] = f(cfg.experts, cfg.d)
+        w[p + "ffn_gate_exps.weight"] = f(cfg.experts, cfg.expert_ffn, cfg.d)
+        w[p + "ffn_up_exps.weight"] = f(cfg.experts, cfg.expert_ffn, cfg.d)
+        w[p + "ffn_down_exps.weight"] = f(cfg.experts, cfg.d, cfg.expert_ffn)
     return w
 
 
 def gguf_quant_kind(g) -> str:
-    """"q4" when most projection weights (2-D blk.* tensors) of a GGUF are 4-bit types (Q4_0, Q4_1,
-    Q4_K), else "bf16"."""
-    proj = [t for n, t in g.tensors.items() if n.startswith("blk.") and len(t.shape) == 2]
+    """"q4" when most projection weights (2-D blk.* tensors, and the stacked 3-D *_exps tensors that hold nearly
+    all of a mixture-of-experts file) of a GGUF are 4-bit types (Q4_0, Q4_1, Q4_K), else "bf16"."""
+    proj = [t for n, t in g.tensors.items() if n.startswith("blk.") and
+            (len(t.shape) == 2 or (len(t.shape) == 3 and n.endswith("_exps.weight")))]
     q4 = sum(t.nelems for t in proj if t.ggml_type in (2, 3, 12))
     return "q4" if proj and q4 * 2 > sum(t.nelems for t in proj) else "bf16"
+
+
+def _moe_config(g, a: str, cfg: DecoderConfig) -> None:
+    """The mixture-of-experts keys of the file into cfg, and the refusal, by name, of what CausalLM does not
+    compute: shared experts, the old one-tensor-per-expert layout, dense and expert layers in one file, and a
+    router wider than the kernel's."""
+    sup = f"(supported: {', '.join(SUPPORTED_ARCHS)}; experts: stacked *_exps tensors in every layer, no shared expert)"
+    names = list(g.tensors)
+    E = int(g.get(f"{a}.expert_count", 0) or 0)
+    shared = [n for n in names if "_shexp" in n]
+    if shared or int(g.get(f"{a}.expert_shared_count", 0) or 0) > 0:
+        what = f"tensor {shared[0]}" if shared else f"{a}.expert_shared_count {int(g.get(f'{a}.expert_shared_count'))}"
+        raise ValueError(f"architecture {a!r} with shared experts ({what}) is not supported {sup}")
+    split = [n for n in names if re.fullmatch(r"blk\.\d+\.ffn_(gate|up|down)\.\d+\.weight", n)]
+    if split:
+        raise ValueError(f"architecture {a!r} with one tensor per expert ({split[0]}) is not supported {sup}")
+    moe = {int(n.split(".")[1]) for n in names if re.fullmatch(r"blk\.\d+\.ffn_gate_inp\.weight", n)}
+    dense = {int(n.split(".")[1]) for n in names if re.fullmatch(r"blk\.\d+\.ffn_gate\.weight", n)}
+    if moe and dense:
+        raise ValueError(f"architecture {a!r} with dense layers ({len(dense)}, first blk.{min(dense)}) beside expert "
+                         f"layers ({len(moe)}, first blk.{min(moe)}) is not supported {sup}")
+    if (E > 0) != bool(moe):
+        raise ValueError(f"architecture {a!r} with {a}.expert_count {E} and {len(moe)} router tensors "
+                         f"(blk.N.ffn_gate_inp.weight) is not supported {sup}")
+    if not E:
+        return
+    k = int(g.get(f"{a}.expert_used_count", 0) or 0)
+    if E > MOE_MAX_EXPERTS or not 1 <= k <= min(MOE_MAX_USED, E):
+        raise ValueError(f"architecture {a!r} with {E} experts, {k} used per token is not supported "
+                         f"(up to {MOE_MAX_EXPERTS} experts, 1 to {MOE_MAX_USED} used and no more than there are) {sup}")
+    cfg.experts, cfg.experts_used = E, k
+    cfg.expert_ffn = int(g.get(f"{a}.expert_feed_forward_length", None) or cfg.ffn)
 
 
 def config_from_gguf(g) -> DecoderConfig:
@@ -159,6 +211,7 @@ def config_from_gguf(g) -> DecoderConfig:
                         arch=a, qkv_bias="blk.0.attn_q.bias" in g.tensors,
                         qk_norm="blk.0.attn_q_norm.weight" in g.tensors,
                         key_length=int(kl) if kl is not None and int(kl) * heads != d else None)
+    _moe_config(g, a, cfg)
     rot = get("rope.dimension_count", None)
     if rot is not None and int(rot) != cfg.head_dim:
         raise ValueError(f"architecture {a!r} with partial rotary (rope.dimension_count {int(rot)} of head dim "
@@ -174,6 +227,29 @@ def config_from_gguf(g) -> DecoderConfig:
     elif kind != "none":
         raise ValueError(f"architecture {a!r} with rope.scaling.type {kind!r} is not supported (none, linear, yarn)")
     return cfg
+
+
+class LazyTensors(Mapping):
+    """name -> tensor, made by ``load(name)`` at every access and not kept: what CausalLM is handed where the
+    whole set of fp32 tensors would not fit in host memory (CausalLM.from_gguf)."""
+
+    def __init__(self, names, load):
+        self._names, self._load = tuple(names), load
+        self._set = frozenset(self._names)
+
+    def __getitem__(self, n):
+        if n not in self._set:
+            raise KeyError(n)
+        return self._load(n)
+
+    def __contains__(self, n):
+        return n in self._set
+
+    def __iter__(self):
+        return iter(self._names)
+
+    def __len__(self):
+        return len(self._names)
 
 
 class Q4Weight:
@@ -212,6 +288,10 @@ class Q4Weight:
     def nbytes(self) -> int:
         return self.q.numel() + self.sm.numel() * 4
 
+    def rows(self, a: int, b: int):
+        """Rows a .. b-1 as a weight of their own, over the same memory (one expert of a stacked matrix)."""
+        return type(self)(self.q[a:b], self.sm[a:b])
+
 
 class Q8Weight(Q4Weight):
     """Q8G32: one byte per weight (u in 0..255) and the same bf16 (d, m) pair per 32-k group,
@@ -240,10 +320,22 @@ class CausalLM:
         self.hip = device != "cpu"
         self.quant = quant if self.hip else "bf16"
         dt = torch.bfloat16 if self.hip else torch.float32
-        T = lambda n: tensors[n].to(device=device, dtype=dt).contiguous()  # noqa: E731
+        hd = cfg.head_dim
+        # NeoX rotation as adjacent pairs: permute the q / k rows of every head (and what goes with them) on
+        # the fp32 tensors, ahead of any 4- / 8-bit re-gridding (groups run along K, so rows move whole).
+        # The cache holds permuted k rows; nothing outside attention reads them.  ``tensors`` may dequantise
+        # on access (LazyTensors), so every tensor is taken once, where it is used.
+        neox = ("attn_q.weight", "attn_k.weight", "attn_q.bias", "attn_k.bias", "attn_q_norm.weight",
+                "attn_k_norm.weight") if cfg.arch in NEOX_ARCHS else ()
+
+        def src(n):
+            t = tensors[n]
+            return neox_rows_to_pairs(t.float(), hd) if n.startswith("blk.") and n.split(".", 2)[2] in neox else t
+
+        T = lambda n: src(n).to(device=device, dtype=dt).contiguous()  # noqa: E731
         self.emb = T("token_embd.weight")
         self.norm_out = T("output_norm.weight").float()
-        head = tensors.get("output.weight", tensors["token_embd.weight"])
+        head = tensors["output.weight" if "output.weight" in tensors else "token_embd.weight"]
         vpad = (cfg.vocab + 127) // 128 * 128
         hw = torch.zeros((vpad, cfg.d), dtype=dt, device=device)
         hw[: cfg.vocab] = head.to(device=device, dtype=dt)
@@ -260,38 +352,51 @@ class CausalLM:
             return (Q8Weight if wide else Q4Weight).quantize(self.L, t)
 
         self.head = Q(self.head, "output.weight" if "output.weight" in tensors else "token_embd.weight")
-        hd = cfg.head_dim
         self.extras = cfg.qkv_bias or cfg.qk_norm  # the fused q/k preparation stands where RoPE stood
-        if cfg.arch in NEOX_ARCHS:
-            # NeoX rotation as adjacent pairs: permute the q / k rows of every head (and what goes with them) on
-            # the fp32 tensors, ahead of any 4- / 8-bit re-gridding (groups run along K, so rows move whole).
-            # The cache holds permuted k rows; nothing outside attention reads them.
-            tensors = dict(tensors)
-            for i in range(cfg.layers):
-                for n in ("attn_q.weight", "attn_k.weight", "attn_q.bias", "attn_k.bias", "attn_q_norm.weight",
-                          "attn_k_norm.weight"):
-                    if f"blk.{i}.{n}" in tensors:
-                        tensors[f"blk.{i}.{n}"] = neox_rows_to_pairs(tensors[f"blk.{i}.{n}"].float(), hd)
-        F32 = lambda n: tensors[n].to(device=device, dtype=torch.float32).contiguous()  # noqa: E731
+        E, EF = cfg.experts, cfg.expert_ffn
+        if E and (E > MOE_MAX_EXPERTS or not 1 <= cfg.experts_used <= min(MOE_MAX_USED, E) or EF < 16 or EF % 16):
+            raise ValueError(f"{E} experts, {cfg.experts_used} used, expert width {EF}: up to {MOE_MAX_EXPERTS} "
+                             f"experts, 1 to {MOE_MAX_USED} used, a width that is a multiple of 16")
+        if E and self.hip and (EF % 64 or EF > GEMV_MAX_K):
+            raise ValueError(f"expert_feed_forward_length {EF} is not supported on the GPU: the expert kernels take "
+                             f"a multiple of 64 up to {GEMV_MAX_K}")
+        # debug hooks of the eager mixture-of-experts layer, both off: a list that collects every layer call's
+        # chosen ids [n, k]; per-layer ids [n, k] used in place of the layer's own choice
+        self.route_log: Optional[list] = None
+        self.route_force: Optional[list] = None
+        F32 = lambda n: src(n).to(device=device, dtype=torch.float32).contiguous()  # noqa: E731
+        from .nomic import pack_upgate
         for i in range(cfg.layers):
             p = f"blk.{i}."
             qkv = torch.cat([T(p + "attn_q.weight"), T(p + "attn_k.weight"), T(p + "attn_v.weight")], 0)
-            gate, up = T(p + "ffn_gate.weight"), T(p + "ffn_up.weight")
-            # SwiGLU epilogue layout: rows interleaved [up16 | gate16] (nomic_api.h NOMIC_EPI_SWIGLU)
-            from .nomic import pack_upgate
-            ug = pack_upgate(up, gate)
-            self.layers.append({"n1": T(p + "attn_norm.weight").float(),
-                                "qkv": Q(qkv.contiguous(), p + "attn_q.weight", p + "attn_k.weight", p + "attn_v.weight"),
-                                "o": Q(T(p + "attn_output.weight"), p + "attn_output.weight"),
-                                "n2": T(p + "ffn_norm.weight").float(),
-                                "ug": Q(ug.contiguous(), p + "ffn_gate.weight", p + "ffn_up.weight"),
-                                "down": Q(T(p + "ffn_down.weight"), p + "ffn_down.weight")})
+            lw = {"n1": T(p + "attn_norm.weight").float(),
+                  "qkv": Q(qkv.contiguous(), p + "attn_q.weight", p + "attn_k.weight", p + "attn_v.weight"),
+                  "o": Q(T(p + "attn_output.weight"), p + "attn_output.weight"),
+                  "n2": T(p + "ffn_norm.weight").float()}
+            if E:
+                # experts stacked along rows: up|gate [E * 2F, d], each expert's 2F rows packed on their own, and
+                # down [E * d, F]; the router stays bf16, with a copy zero-padded to the GEMM's 128-row multiple
+                up, gate = T(p + "ffn_up_exps.weight"), T(p + "ffn_gate_exps.weight")
+                ug = torch.cat([pack_upgate(up[e], gate[e]) for e in range(E)], 0)
+                del up, gate
+                lw["ug"] = Q(ug.contiguous(), p + "ffn_gate_exps.weight", p + "ffn_up_exps.weight")
+                lw["down"] = Q(T(p + "ffn_down_exps.weight").reshape(E * cfg.d, EF), p + "ffn_down_exps.weight")
+                rp = torch.zeros(((E + 127) // 128 * 128, cfg.d), dtype=dt, device=device)
+                rp[:E] = T(p + "ffn_gate_inp.weight")
+                lw["router_pad"], lw["router"] = rp, rp[:E]
+            else:
+                gate, up = T(p + "ffn_gate.weight"), T(p + "ffn_up.weight")
+                # SwiGLU epilogue layout: rows interleaved [up16 | gate16] (nomic_api.h NOMIC_EPI_SWIGLU)
+                ug = pack_upgate(up, gate)
+                lw["ug"] = Q(ug.contiguous(), p + "ffn_gate.weight", p + "ffn_up.weight")
+                lw["down"] = Q(T(p + "ffn_down.weight"), p + "ffn_down.weight")
+                del gate, up
+            self.layers.append(lw)
             # the architecture's extras, fp32: the fused bias [(H + 2 KVH) hd] and the per-head norm weights [hd]
-            lw = self.layers[-1]
             lw["qkv_b"] = torch.cat([F32(p + f"attn_{c}.bias") for c in "qkv"]) if cfg.qkv_bias else None
             lw["qn"] = F32(p + "attn_q_norm.weight") if cfg.qk_norm else None
             lw["kn"] = F32(p + "attn_k_norm.weight") if cfg.qk_norm else None
-            del qkv, gate, up, ug
+            del qkv, ug
         self._q4_scratch: Optional[torch.Tensor] = None
         # RoPE tables (host only; the kernels read cos / sin): inv_freq[j] over rope_freqs.weight[j] where the
         # file has that tensor (llama 3.1+), positions over the linear scaling factor
@@ -310,8 +415,9 @@ class CausalLM:
         self.pos = 0
         self.attn_kernel = True  # HIP prefill / decode attention (False: torch SDPA, for A/B only)
         if self.hip:
-            ok = all(n % 128 == 0 for n in (cfg.q_dim + 2 * cfg.kv_heads * hd, cfg.d, 2 * cfg.ffn, vpad)) \
-                and cfg.d % 64 == 0 and cfg.ffn % 64 == 0 and cfg.q_dim % 64 == 0
+            ffn = EF if E else cfg.ffn
+            ok = all(n % 128 == 0 for n in (cfg.q_dim + 2 * cfg.kv_heads * hd, cfg.d, 2 * ffn, vpad)) \
+                and cfg.d % 64 == 0 and ffn % 64 == 0 and cfg.q_dim % 64 == 0
             if not ok:
                 raise ValueError("decoder dims must be multiples of 128 (N) / 64 (K) for the MFMA GEMM")
             if self.extras and hd not in (64, 128):
@@ -402,6 +508,19 @@ class CausalLM:
             self.L.dec_qk_prep_kv_seg.argtypes = self.L.dec_rope_kv_seg.argtypes[:-1] + ex
             for name in ("dec_qk_prep", "dec_qk_prep_kv", "dec_qk_prep_kv_b", "dec_qk_prep_kv_seg"):
                 getattr(self.L, name).restype = c_int
+            # mixture of experts (csrc/hip/decoder_moe.hip): ids / k / E follow the weight planes
+            moe = {"dec_moe_route": [P, c_long, c_int, c_int, c_int, P, P, P],
+                   "dec_gemv_moe": [P, P, c_float, P, c_int, c_int, P, c_int, c_int, P, P],
+                   "dec_gemv_moe_q4": [P, P, c_float, P, P, c_int, c_int, P, c_int, c_int, P, P],
+                   "dec_gemv_moe_down": [P, P, c_int, c_int, P, P, c_int, c_int, P, P, P],
+                   "dec_gemv_moe_down_q4": [P, P, P, c_int, c_int, P, P, c_int, c_int, P, P, P],
+                   "dec_moe_plan": [P, c_int, c_int, c_int, c_int, P, P, P, P],
+                   "dec_moe_gather": [P, c_long, c_int, c_int, c_int, P, c_int, P, P],
+                   "dec_moe_combine": [P, c_int, c_int, c_int, c_int, P, P, P, c_long, P, c_long, P]}
+            moe["dec_gemv_moe_q8"], moe["dec_gemv_moe_down_q8"] = moe["dec_gemv_moe_q4"], moe["dec_gemv_moe_down_q4"]
+            for name, args in moe.items():
+                getattr(self.L, name).argtypes = args
+                getattr(self.L, name).restype = c_int
             self.L._dec_declared = True
 
     def _prep_args(self, lw) -> tuple:
@@ -424,7 +543,9 @@ class CausalLM:
         cfg = config_from_gguf(g)
         if quant == "auto":
             quant = gguf_quant_kind(g)
-        tensors = {n: torch.from_numpy(np.ascontiguousarray(g.to_numpy_f32(n))) for n in g.tensors}
+        # fp32 on access, one tensor at a time: a mixture-of-experts file's stacked experts never stand in host
+        # memory as fp32 all at once (CausalLM takes a layer's, converts them and lets go)
+        tensors = LazyTensors(g.tensors, lambda n: torch.from_numpy(np.ascontiguousarray(g.to_numpy_f32(n))))
         from .llm_tokenizer import tokenizer_from_gguf
         tok = tokenizer_from_gguf(g) or ByteTokenizer()  # SPM / BPE by tokenizer.ggml.model
         if not hasattr(tok, "chat_template"):
@@ -497,6 +618,79 @@ class CausalLM:
     def reset(self):
         self.pos = 0
 
+    # ------------------------------------------------------ mixture of experts --
+    def _moe(self, li: int, lw, h: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+        """x + sum over each token's k experts of weight * down_e(SwiGLU(up|gate_e(h))) for the n >= 1 rows of
+        h (the normalised x).  Routing: the k largest router logits (ties to the lower index), weighted by
+        their softmax probabilities renormalised over the k.  On the GPU the rows are grouped by expert into
+        128-row aligned segments (dec_moe_plan / dec_moe_gather), each non-empty expert runs the two MFMA
+        GEMMs on its segment, and dec_moe_combine sums back; one host read (the counts) per layer."""
+        cfg = self.cfg
+        E, k, F, d = cfg.experts, cfg.experts_used, cfg.expert_ffn, cfg.d
+        n = h.shape[0]
+        forced = None
+        if self.route_force is not None:
+            forced = torch.as_tensor(self.route_force[li], device=self.device).reshape(n, k)
+            if int(forced.min()) < 0 or int(forced.max()) >= E:
+                raise ValueError(f"route_force names an expert outside 0..{E - 1}")
+        if not self.hip:
+            logits = (h @ lw["router"].T).float()
+            ids = torch.sort(logits, dim=-1, descending=True, stable=True).indices[:, :k] if forced is None \
+                else forced.long()
+            w = torch.softmax(logits.gather(1, ids), -1)
+            if self.route_log is not None:
+                self.route_log.append(ids.to(torch.int32).clone())
+            acc = torch.zeros_like(x)
+            for e in ids.unique().tolist():
+                t, j = (ids == e).nonzero(as_tuple=True)
+                up, gate = self._split_ug(h[t] @ lw["ug"][e * 2 * F: (e + 1) * 2 * F].T)
+                y = (up * torch.nn.functional.silu(gate)) @ lw["down"][e * d: (e + 1) * d].T
+                acc.index_add_(0, t, w[t, j, None].to(y.dtype) * y)
+            return x + acc
+        from .nomic import _chk, _stream
+        L, s = self.L, _stream()
+        i32 = dict(dtype=torch.int32, device=self.device)
+        logits = self._mm(4, h, lw["router_pad"], lw["router_pad"].shape[0])
+        ids = torch.empty((n, k), **i32)
+        w = torch.empty((n, k), dtype=torch.float32, device=self.device)
+        _chk(L.dec_moe_route(logits.data_ptr(), logits.stride(0), n, E, k, ids.data_ptr(), w.data_ptr(), s), "moe_route")
+        if forced is not None:  # the forced set, weighted by this layer's own probabilities over it
+            ids = forced.to(torch.int32).contiguous()
+            w = torch.softmax(logits[:, :E].gather(1, ids.long()), -1).contiguous()
+        if self.route_log is not None:
+            self.route_log.append(ids.clone())
+        counts, base = torch.empty(E, **i32), torch.empty(E, **i32)
+        slot = torch.full((n, k), -1, **i32)
+        _chk(L.dec_moe_plan(ids.data_ptr(), n, k, E, 128, counts.data_ptr(), base.data_ptr(), slot.data_ptr(), s),
+             "moe_plan")
+        cnt = counts.tolist()  # the layer's one host read; the starts follow from the counts
+        rows, start = 0, []
+        for c in cnt:
+            start.append(rows)
+            rows += (c + 127) // 128 * 128
+        # the GEMM reads whole 128-row tiles: rows no token fills are zero, so that every product is finite
+        xg = torch.zeros((rows, d), dtype=torch.bfloat16, device=self.device)
+        h = h.contiguous()
+        _chk(L.dec_moe_gather(h.data_ptr(), h.stride(0), n, k, d, slot.data_ptr(), rows, xg.data_ptr(), s), "moe_gather")
+        f = torch.empty((rows, F), dtype=torch.bfloat16, device=self.device)
+        y = torch.empty((rows, d), dtype=torch.float32, device=self.device)
+        part = lambda m, a, b: m.rows(a, b) if isinstance(m, Q4Weight) else m[a:b]  # noqa: E731
+        for e, c in enumerate(cnt):
+            if not c:
+                continue
+            r0 = start[e]
+            ug = self._dense(part(lw["ug"], e * 2 * F, (e + 1) * 2 * F))  # a 4- / 8-bit slice: into the scratch
+            _chk(L.nomic_gemm(2, xg[r0:].data_ptr(), d, ug.data_ptr(), d, c, 2 * F, d, f[r0:].data_ptr(), F, None, F,
+                              None, None, 0, s), "gemm up|gate (expert)")
+            dn = self._dense(part(lw["down"], e * d, (e + 1) * d))
+            _chk(L.nomic_gemm(4, f[r0:].data_ptr(), F, dn.data_ptr(), F, c, d, F, y[r0:].data_ptr(), d, None, d,
+                              None, None, 0, s), "gemm down (expert)")
+        x = x.contiguous()
+        out = torch.empty_like(x)
+        _chk(L.dec_moe_combine(y.data_ptr(), rows, n, k, d, slot.data_ptr(), w.data_ptr(), x.data_ptr(), d,
+                               out.data_ptr(), d, s), "moe_combine")
+        return out
+
     @torch.no_grad()
     def forward(self, ids: List[int]) -> torch.Tensor:
         """Append tokens to the KV cache; returns fp32 logits of the last position."""
@@ -566,6 +760,9 @@ class CausalLM:
                 a = a.transpose(0, 1).reshape(n, qd).contiguous()
             x = self._mm(1, a, lw["o"], cfg.d, res=x)
             h = self._rms(x, lw["n2"])
+            if cfg.experts:
+                x = self._moe(li, lw, h, x)
+                continue
             f = self._mm(2, h, lw["ug"], cfg.ffn)
             x = self._mm(1, f.contiguous(), lw["down"], cfg.d, res=x)
         self.pos += n
@@ -623,7 +820,13 @@ class DecodeEngine:
         self.xb = torch.empty(cfg.d, **e)
         self.qkv = torch.empty(cfg.q_dim + 2 * kvd, **e)
         self.attn = torch.empty(cfg.q_dim, **e)
-        self.ffn = torch.empty(cfg.ffn, **e)
+        self.ffn = torch.empty(cfg.experts_used * cfg.expert_ffn if cfg.experts else cfg.ffn, **e)
+        # mixture of experts: the router's logits, and per layer the step's chosen experts and their weights
+        # (kept per layer so that a step's choices can be read afterwards)
+        k = cfg.experts_used
+        self.router_logits = torch.zeros(max(cfg.experts, 1), dtype=torch.float32, device=dev)
+        self.moe_ids = [torch.zeros(k, dtype=torch.int32, device=dev) for _ in range(cfg.layers if k else 0)]
+        self.moe_w = [torch.zeros(k, dtype=torch.float32, device=dev) for _ in range(cfg.layers if k else 0)]
         self.logits = torch.empty(m.head.shape[0], dtype=torch.float32, device=dev)
         self.attn_ws = torch.empty(cfg.heads * 32 * (cfg.head_dim + 2), dtype=torch.float32, device=dev)  # split-L
         self.samp_ws = torch.empty(m.L.dec_sample_ws_floats(), dtype=torch.float32, device=dev)  # multi-block sampler
@@ -667,6 +870,29 @@ class DecodeEngine:
                                       hd, hd ** -0.5, self.attn.data_ptr(), self.st.data_ptr(),
                                       self.attn_ws.data_ptr(), s), "attn_decode")
             gemv(1, self.attn, None, lw["o"], cfg.d, cfg.q_dim, self.xa, self.xb, "gemv o")
+            if cfg.experts:
+                # four launches where the dense layer has two: router logits (RMSNorm fused), the choice, then
+                # the k experts' up|gate and down, each reading the ids the choice left on the device
+                E, k, F = cfg.experts, cfg.experts_used, cfg.expert_ffn
+                ids, wts, ug, dn = self.moe_ids[li], self.moe_w[li], lw["ug"], lw["down"]
+                x, n2, f = self.xb.data_ptr(), lw["n2"].data_ptr(), self.ffn.data_ptr()
+                gemv(4, self.xb, lw["n2"], lw["router"], E, cfg.d, None, self.router_logits, "gemv router")
+                _chk(L.dec_moe_route(self.router_logits.data_ptr(), E, 1, E, k, ids.data_ptr(), wts.data_ptr(), s),
+                     "moe_route")
+                if isinstance(ug, Q4Weight):
+                    _chk(getattr(L, f"dec_gemv_moe_q{ug.bits}")(x, n2, cfg.eps, ug.q.data_ptr(), ug.sm.data_ptr(), 2 * F,
+                                                                cfg.d, ids.data_ptr(), k, E, f, s), "gemv_moe up|gate")
+                else:
+                    _chk(L.dec_gemv_moe(x, n2, cfg.eps, ug.data_ptr(), 2 * F, cfg.d, ids.data_ptr(), k, E, f, s),
+                         "gemv_moe up|gate")
+                if isinstance(dn, Q4Weight):
+                    _chk(getattr(L, f"dec_gemv_moe_down_q{dn.bits}")(f, dn.q.data_ptr(), dn.sm.data_ptr(), cfg.d, F,
+                                                                     ids.data_ptr(), wts.data_ptr(), k, E, x,
+                                                                     self.xa.data_ptr(), s), "gemv_moe down")
+                else:
+                    _chk(L.dec_gemv_moe_down(f, dn.data_ptr(), cfg.d, F, ids.data_ptr(), wts.data_ptr(), k, E, x,
+                                             self.xa.data_ptr(), s), "gemv_moe down")
+                continue
             gemv(2, self.xb, lw["n2"], lw["ug"], lw["ug"].shape[0], cfg.d, None, self.ffn, "gemv up|gate")
             gemv(1, self.ffn, None, lw["down"], cfg.d, cfg.ffn, self.xb, self.xa, "gemv down")
         gemv(4, self.xa, m.norm_out, m.head, m.head.shape[0], cfg.d, None, self.logits, "gemv head")
@@ -751,6 +977,8 @@ class BatchDecodeEngine:
         assert model.hip, "BatchDecodeEngine runs on the GPU"
         if not 2 <= max_seqs <= 16:
             raise ValueError(f"max_seqs must be 2..16, not {max_seqs}")
+        if model.cfg.experts:
+            raise ValueError("the batched decode engine has no mixture-of-experts step (use DecodeEngine)")
         if not model.decode_kernel:
             raise ValueError(f"head dim {model.cfg.head_dim}: the batched decode engine needs a multiple of 64 "
                              "up to 256 (use CausalLM.forward)")
